@@ -18,6 +18,14 @@ path), and one RCCL all_gather of the int32 codes closes each generate. Codes ar
 reduction order depends on the M regime). value = codes of all ranks /
 max-over-ranks wall time ("scaling": "weak").
 
+A plain run sets up, warms up, times the steps and prints the result line (codes/s, RTF, ms_per_step,
+the generate/DAC breakdown and the whole-step roofline, all from the timed steps themselves). `--full`
+adds everything that takes runs of its own: the dominant kernel's and the GEMMs' rooflines (HIP events
+on isolated launches), the CPU baseline (oracle) and the secondary configurations (c2, c3 through
+Zonos.generate, c5). `--dump-outputs DIR` writes what the last timed step returned to its caller (the
+codes of generate_sharded, the waveforms of the DAC decode) as DIR/<name>.npy (float32, rank 0); inputs
+and sampling noise are seeded, so two builds run with the same arguments can be compared array for array.
+
 Prints ONE JSON line on rank 0. `--stub` replaces the GPU workload by a CPU stand-in (gloo) so
 the launcher and the reporting path can be tested without a GPU (tests/test_bench_cpu.py).
 """
@@ -51,7 +59,13 @@ def parse():
     ap.add_argument("--model", choices=["transformer", "hybrid"], default="transformer",
                     help="hybrid = Zonos-v0.1-hybrid geometry as assumed in synthetic.ZONOS_V01_HYBRID (config 5)")
     ap.add_argument("--no-dac", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what takes runs of its own: kernel and GEMM rooflines, "
+                         "the CPU baseline and the secondary configurations (see --no-cpu-baseline, --no-secondary)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step returned (codes, waveforms) as DIR/<name>.npy, float32; "
+                         "a fixed seeded sample of an array that is too large (64 MB at most in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-sample-steps", type=int, default=1)
     ap.add_argument("--stub", action="store_true", help="CPU stand-in workload (launcher/reporting tests)")
     ap.add_argument("--graph-steps", type=int, default=None,
@@ -60,7 +74,8 @@ def parse():
                     help="1: decode each step's codes to waveforms on a side stream while the next step's generate "
                          "runs (the DAC's MFMA-bound convs beside the HBM-bound decode); 0: serial")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the secondary measurements after a 1-GPU c3 run (c2, c5, c3 through Zonos.generate)")
+                    help="with --full: skip the secondary measurements after a 1-GPU c3 run (c2, c5, c3 through "
+                         "Zonos.generate)")
     return ap.parse_args()
 
 
@@ -354,6 +369,50 @@ def cpu_baseline(args):
                 step_s=round(step_s, 4), dac_ms_per_frame=round(dac_s_per_frame * 1e3, 2))
 
 
+# ------------------------------------------------------------------------------ output dump
+DUMP_BLOCK = 4096                 # elements per sampled block
+DUMP_BUDGET = {"codes": 12e6, "codes_all": 12e6, "wav": 32e6}     # bytes of float32 per array (56 MB in all)
+
+
+def _stack_padded(torch, seq, fill):
+    """[n, ...] from a list of tensors whose last dimension may differ (padded with `fill`)."""
+    T = max(int(t.shape[-1]) for t in seq)
+    return torch.stack([torch.nn.functional.pad(t, (0, T - int(t.shape[-1])), value=fill) for t in seq])
+
+
+def _fixed_sample(torch, t, max_bytes, seed=0):
+    """t as flat float32; if that exceeds max_bytes, the same seeded choice of DUMP_BLOCK-element blocks of
+    it on every run (sorted, so the sample keeps the array's order)."""
+    import numpy as np
+    flat = t.reshape(-1)
+    n, keep = flat.numel(), int(max_bytes // 4)
+    if n > keep:
+        pick = np.sort(np.random.default_rng(seed).choice(n // DUMP_BLOCK, keep // DUMP_BLOCK, replace=False))
+        idx = (pick[:, None] * DUMP_BLOCK + np.arange(DUMP_BLOCK)[None, :]).reshape(-1)
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+    return flat.to(torch.float32).cpu().numpy()
+
+
+def dump_outputs(dirname, last):
+    """--dump-outputs: what the last timed step returned, name -> list of per-utterance tensors. Codes keep
+    their [n, 9, T] shape (shorter utterances padded with -1) unless they have to be sampled; the waveforms
+    are concatenated in utterance order."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    for name, seq in last.items():
+        if not seq:
+            continue
+        if name == "wav":
+            arr = _fixed_sample(torch, torch.cat([w.reshape(-1) for w in seq]), DUMP_BUDGET[name])
+        else:
+            full = _stack_padded(torch, seq, -1)
+            arr = _fixed_sample(torch, full, DUMP_BUDGET[name])
+            if arr.size == full.numel():
+                arr = arr.reshape(tuple(full.shape))
+        np.save(os.path.join(dirname, name + ".npy"), arr)
+
+
 # ------------------------------------------------------------------------------ workloads
 class StubWorkload:
     """CPU stand-in with the real workload's interface: 'generates' B utterances of new_tokens
@@ -364,16 +423,19 @@ class StubWorkload:
         self.args, self.rank, self.dist, self.torch = args, rank, dist, torch
         self.stats = {"gen_s": 0.0, "dac_s": 0.0}
         self.model_name = "stub"
+        self.last = {}
 
     def step(self, i, timed):
         torch = self.torch
         B, T = self.args.batch, self.args.new_tokens
         time.sleep(0.01 * (1 + self.rank))
         codes = [torch.full((9, T), self.rank * B + b, dtype=torch.int64) for b in range(B)]
+        self.last = {"codes": codes}
         if self.dist is not None:
             from zonos_amd.distributed import gather_codes
             allc = gather_codes(codes)
             assert len(allc) == B * self.dist.get_world_size()
+            self.last["codes_all"] = allc
         return B * T
 
     def sync(self):
@@ -418,6 +480,7 @@ class GpuWorkload:
                            else "Zonos-v0.1-hybrid (assumed geometry)")
         self.side = torch.cuda.Stream(dev) if args.dac_overlap else None
         self.dac_events = []
+        self.last = {}                  # what the latest step returned (--dump-outputs)
 
     def step(self, i, timed):
         torch, args = self.torch, self.args
@@ -434,10 +497,12 @@ class GpuWorkload:
         assert len(codes) == args.batch and len(allc) == args.batch * self.world
         torch.cuda.synchronize(self.dev)
         t1 = time.time()
-        if self.dac is not None:
-            self.dac.decode_list(codes)
+        wavs = self.dac.decode_list(codes) if self.dac is not None else []
         torch.cuda.synchronize(self.dev)
         t2 = time.time()
+        self.last = {"codes": codes, "wav": wavs}
+        if self.world > 1:
+            self.last["codes_all"] = allc
         if timed:
             self.stats["gen_s"] += t1 - t0
             self.stats["dac_s"] += t2 - t1
@@ -460,6 +525,9 @@ class GpuWorkload:
         t1 = time.time()
         if timed:
             self.stats["gen_s"] += t1 - t0
+        self.last = {"codes": codes, "wav": []}
+        if self.world > 1:
+            self.last["codes_all"] = allc
         if self.dac is not None:
             self.side.wait_stream(main)
             with torch.cuda.stream(self.side):
@@ -467,7 +535,7 @@ class GpuWorkload:
                     c.record_stream(self.side)
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record(self.side)
-                self.dac.decode_list(codes)
+                self.last["wav"] = self.dac.decode_list(codes)
                 e1.record(self.side)
             if timed:
                 self.dac_events.append((e0, e1))
@@ -483,12 +551,14 @@ class GpuWorkload:
         R = 2 * args.batch
         n_dec = args.new_tokens + 8                       # decode steps per generate (max_steps)
         ctx_mean = args.lc + args.prefix + 1 + n_dec // 2
-        if args.model == "hybrid":
-            roof = mamba_roofline(eng)
-        elif eng._small(R):
-            roof = gemv_roofline(eng)
-        else:
-            roof = attn_roofline(eng, ctx_mean)
+        extra = {}
+        if args.full:                   # isolated launches of the dominant kernel, timed with HIP events
+            if args.model == "hybrid":
+                extra["roofline"] = mamba_roofline(eng)
+            elif eng._small(R):
+                extra["roofline"] = gemv_roofline(eng)
+            else:
+                extra["roofline"] = attn_roofline(eng, ctx_mean)
         gen_step_s = self.stats["gen_s"] / args.steps
         dec_ms = gen_step_s / n_dec * 1e3
         sb = step_bytes(eng, R, ctx_mean)
@@ -497,10 +567,10 @@ class GpuWorkload:
                          frac=round(sb / (dec_ms / 1e3) / 1e9 / HBM_PEAK_GBS, 4),
                          note="algorithmic bytes per decode step at the mean context / (generate wall time / decode "
                               "steps, prefill included)")
-        extra = {}
-        if args.model != "hybrid" and not eng._small(R) and R <= 128:
+        extra["step_roofline"] = step_roof
+        if args.full and args.model != "hybrid" and not eng._small(R) and R <= 128:
             extra["gemm_roofline"] = gemm_roofline(eng)
-        return dict(roofline=roof, step_roofline=step_roof, **extra,
+        return dict(**extra,
                     breakdown={"generate_s_per_step": round(gen_step_s, 3),
                                "dac_s_per_step": round(self.stats["dac_s"] / args.steps, 3),
                                "dac_overlap": bool(args.dac_overlap),
@@ -704,10 +774,12 @@ def main():
                        "seq_len": args.lc + args.prefix + args.new_tokens + 9, "parallelism": f"dp{world}"},
             "rtf": round(audio_s / elapsed, 2),
         }
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, wl.last)
         out.update(wl.report(elapsed, args))
-        if not args.stub and not args.no_cpu_baseline and world == 1 and args.model == "transformer":
+        if args.full and not args.stub and not args.no_cpu_baseline and world == 1 and args.model == "transformer":
             out["cpu_baseline"] = cpu_baseline(args)
-        if (not args.stub and not args.no_secondary and world == 1 and cfg_name == "c3"
+        if (args.full and not args.stub and not args.no_secondary and world == 1 and cfg_name == "c3"
                 and args.model == "transformer" and not args.layers):
             out["secondary"] = secondary_runs(args, wl, out["value"])
         print(json.dumps(out), flush=True)

@@ -10,4 +10,4 @@ timeout -s KILL 120 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $O/w -o run --o
 python tools/gemm_pmc.py --summary $O/f $O/w --json $O/r5_gemm_pmc.json &&
 cp $O/r5_gemm_pmc.json profiles/ &&
 find $O -name "*.csv" -path "*_SIZE*" -delete; 
-timeout -k 10 600 python -u bench.py > $O/bench_c3.json.log 2>&1 && grep '^{' $O/bench_c3.json.log | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], json.dumps(d.get('gemm_roofline')))"
+timeout -k 10 600 python -u bench.py --full > $O/bench_c3.json.log 2>&1 && grep '^{' $O/bench_c3.json.log | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], json.dumps(d.get('gemm_roofline')))"
