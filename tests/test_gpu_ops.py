@@ -370,7 +370,7 @@ def test_embed_codes():
                                            (1, 2048, 4096, 2, False), (2, 16384, 2048, 1, True),
                                            (9, 16384, 2048, 1, True), (7, 4000, 2048, 0, False),
                                            (3, 5000, 2048, 0, True), (4, 5000, 8192, 2, False),
-                                           # B = 1 (M <= 2): activation staged in LDS per wave (ZK_GF_XC) at
+                                           # B = 1 (M <= 2): activation staged in LDS per wave (k_gemv_f's XC form) at
                                            # every K and layout, LayerNorm loads by the normalising waves only
                                            (2, 2048, 8192, 2, False), (1, 4000, 2048, 0, False),
                                            (2, 16384, 4096, 1, False), (2, 9234, 8192, 0, False),

@@ -1,5 +1,5 @@
 #!/bin/bash
-# One parametrised A/B / evidence driver for GPU boxes (replaces the round-1/2 one-off scripts).
+# One parametrised A/B / evidence driver for GPU boxes (replaces the one-off scripts of every round).
 #
 #   tools/gpu_ab.sh OUT STEP [STEP ...]
 #
@@ -12,6 +12,10 @@
 #                         zonos_amd.build.build_variant), twice, interleaved
 #   benchv:NAME[:ARGS]    bench.py ARGS on the product library and every variant, twice,
 #                         interleaved -> OUT/benchv_NAME.log (value + decode ms per step)
+#   toolv:SCRIPT[:ARGS]   python tools/SCRIPT ARGS (comma-separated; a developer tool that prints its own
+#                         result lines: c2_step.py, c3_splits.py, c5_inp.py, ...) on the product library
+#                         and every variant, twice, interleaved -> OUT/toolv_SCRIPT.log (appended, so
+#                         several steps with different ARGS sweep an argument)
 #   testsv:PYTEST_K       pytest -m gpu -k PYTEST_K on every variant (parity must hold for any tuning)
 #   prof:NAME[:ARGS]      rocprofv3 --kernel-trace --stats of bench.py ARGS -> OUT/prof_NAME/*stats.csv
 #   pmcstd:ROUND          HBM bytes per launch of the decode attention (c3 shape, tools/attn_pmc.py) and
@@ -55,6 +59,16 @@ for step in "$@"; do
       done > "$OUT/benchv_$name.log" 2>&1
       rm -f "$OUT/benchv_tmp.log"
       cat "$OUT/benchv_$name.log" ;;
+    toolv)
+      name=${rest%%:*}; a=${rest#*:}; [ "$a" = "$rest" ] && a=""
+      for i in 1 2; do
+        for v in product $(ls zonos_amd/lib/variants 2>/dev/null); do
+          lp=""; [ "$v" != product ] && lp=zonos_amd/lib/variants/$v/libzonos_hip.so
+          echo "== $v $name $a"
+          ZK_LIB_PATH=$lp timeout -k 10 400 python -u tools/$name ${a//,/ } 2>&1
+        done
+      done >> "$OUT/toolv_$name.log"
+      grep -v amdgpu "$OUT/toolv_$name.log" | tail -n 40 ;;
     testsv)
       for v in $(ls zonos_amd/lib/variants 2>/dev/null); do
         ZK_LIB_PATH=zonos_amd/lib/variants/$v/libzonos_hip.so timeout -k 10 600 python -u -m pytest tests -m gpu -x -q \

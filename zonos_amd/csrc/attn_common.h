@@ -40,9 +40,6 @@ ZK_DEV void rope_dims(int j, int hd, int& d0, int& d1) {
 }
 
 // ------------------------------------------------------------------ decode attention
-#ifndef ZK_ATT_TRIM
-#define ZK_ATT_TRIM 1      // per-wave key-slice trimming (0: whole 128-key blocks, clamped tail load)
-#endif
 constexpr int AT_KB = 128;      // keys per workgroup iteration (4 waves x 32)
 constexpr int AT_G = 4;         // query heads per KV head handled by the B operand (<= 16)
 constexpr int AT_STR = 2 * AT_G + AT_G * 128;   // work floats per (r, g, split)
@@ -322,16 +319,12 @@ ZK_DEV void attn_decode_wg(AttnSmem& sm, const Bar& bar, const Issued& issued, i
 
     bf16x8 qf[4];
     KVFrag fa, fb;
-#if ZK_ATT_TRIM
     // This wave's 32-key slice of block b holds keys b*128 + 32w ..: it loads and multiplies only
     // the blocks whose slice holds a visible key (b*128 + 32w < ctx) and never re-loads the last
     // one. (Reading whole 128-key blocks plus a clamped tail prefetch fetched 11 % more than the
     // algorithmic bytes at ctx 1705; a fully masked slice adds exactly nothing to (m, l, O).)
     const int vis = ctx - 32 * w;
     const int kbw = vis <= 0 ? kb0 : max(kb0, min(kb1, (vis + AT_KB - 1) / AT_KB));
-#else
-    const int kbw = kb1;
-#endif
     const int last = kbw - 1;
     // the first key block can be fetched before the prologue unless it holds the new key
     // FUSED: the new key's cache lines are written only at the end of the kernel (a store
@@ -344,7 +337,7 @@ ZK_DEV void attn_decode_wg(AttnSmem& sm, const Bar& bar, const Issued& issued, i
     const bool early = FUSED && (PGS > 0 || kbw > kb0);
     if (early) {      // the first TWO key blocks are in flight during the prologue
         load_kv<KVNT>(fa, kb, vb, Smax, kb0 * AT_KB + 32 * w, ln, lg);
-        if (PGS > 0 || !ZK_ATT_TRIM || kb0 + 1 < kbw)
+        if (PGS > 0 || kb0 + 1 < kbw)
             load_kv<KVNT>(fb, kb, vb, Smax, min(kb0 + 1, max(last, kb0)) * AT_KB + 32 * w, ln, lg);
     }
     if (issued()) {          // skip: nothing is written (the loads above are in bounds)
@@ -432,12 +425,6 @@ ZK_DEV void attn_decode_wg(AttnSmem& sm, const Bar& bar, const Issued& issued, i
             }
         }
         bar();      // q, new k, new v in LDS
-#ifdef ZK_ATT_DBGQ
-        if (q != nullptr && split == 0)
-            for (int i = threadIdx.x; i < G * HD / 2; i += 256)
-                reinterpret_cast<uint32_t*>(const_cast<bf16_t*>(q))[((size_t)r * H + g * G) * (HD / 2) + i] =
-                    s_q[i / (HD / 2)][i % (HD / 2)];
-#endif
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
             uint4 v = make_uint4(0, 0, 0, 0);
@@ -463,11 +450,11 @@ ZK_DEV void attn_decode_wg(AttnSmem& sm, const Bar& bar, const Issued& issued, i
     if (kbw > kb0) {
         if (!early) load_kv<KVNT>(fa, kb, vb, Smax, kb0 * AT_KB + 32 * w, ln, lg);
         for (int it = kb0; it < kbw; it += 2) {
-            if (!(early && it == kb0) && (!ZK_ATT_TRIM || it + 1 < kbw))
+            if (!(early && it == kb0) && it + 1 < kbw)
                 load_kv<KVNT>(fb, kb, vb, Smax, min(it + 1, last) * AT_KB + 32 * w, ln, lg);
             if (FUSED) patch_kv(fa, s_kn, s_vn, it * AT_KB + 32 * w, pos, ln, lg);
             attn_step(st, fa, qf, it * AT_KB + 32 * w, ctx, scale, lg);
-            if (!ZK_ATT_TRIM || it + 2 < kbw) load_kv<KVNT>(fa, kb, vb, Smax, min(it + 2, last) * AT_KB + 32 * w, ln, lg);
+            if (it + 2 < kbw) load_kv<KVNT>(fa, kb, vb, Smax, min(it + 2, last) * AT_KB + 32 * w, ln, lg);
             if (it + 1 < kbw) {
                 if (FUSED) patch_kv(fb, s_kn, s_vn, (it + 1) * AT_KB + 32 * w, pos, ln, lg);
                 attn_step(st, fb, qf, (it + 1) * AT_KB + 32 * w, ctx, scale, lg);

@@ -292,9 +292,6 @@ __global__ __launch_bounds__(LN_NT) void k_resid_ln_var(const float* part, int n
 // NS > 0: exactly NS slabs (only real slabs loaded); NS = 0: nsplit <= RL_MAXS with clamped loads
 // WARM: a ninth wave warms the next GEMM's first weight chunks into L2 (warm.h) and keeps the
 // block's barrier count (two per row) without waiting for its loads.
-#ifndef ZK_RL_DEFER
-#define ZK_RL_DEFER 1              // step word tested after the row's loads are issued (see below)
-#endif
 template <int NS, bool WARM = false>
 __global__ __launch_bounds__(WARM ? 576 : 512) void k_resid_ln_d2k512(const float* part, int nsplit, const bf16_t* x_in,
                                                          const bf16_t* w, const bf16_t* b, float eps, int rows,
@@ -303,8 +300,8 @@ __global__ __launch_bounds__(WARM ? 576 : 512) void k_resid_ln_d2k512(const floa
                                                          int wgz, int wch) {
     constexpr int D = 2048;
     __shared__ float red[16];
-    if (!ZK_RL_DEFER || (WARM && threadIdx.x >= 512))
-        if (skip && *skip) return;
+    if (WARM && threadIdx.x >= 512)         // (two tests of one condition: folded into one block, hipcc
+        if (skip && *skip) return;          // emits different code for the WARM instantiations)
     if (WARM && threadIdx.x >= 512) {
         __shared__ __attribute__((aligned(16))) char sink[1024];
         warm_units(wW, wK, wgx, wgz, wch, blockIdx.x, gridDim.x, 0, 1, threadIdx.x & 63, sink);
@@ -325,16 +322,14 @@ __global__ __launch_bounds__(WARM ? 576 : 512) void k_resid_ln_d2k512(const floa
 #pragma unroll
     for (int sp = 0; sp < NL; ++sp)
         a0[sp] = *reinterpret_cast<const float4*>(p + (size_t)(NS ? sp : min(sp, nsplit - 1)) * slab + c0);
-    if constexpr (ZK_RL_DEFER) {
-        // the step word after the row's loads (all in bounds): its round trip overlaps theirs
-        if (ld_word_here(skip)) {
-            keep_live(w0);
-            keep_live(b0);
-            keep_live(x0);
+    // the step word after the row's loads (all in bounds): its round trip overlaps theirs
+    if (ld_word_here(skip)) {
+        keep_live(w0);
+        keep_live(b0);
+        keep_live(x0);
 #pragma unroll
-            for (int sp = 0; sp < NL; ++sp) keep_live(a0[sp]);
-            return;
-        }
+        for (int sp = 0; sp < NL; ++sp) keep_live(a0[sp]);
+        return;
     }
     float acc[4] = {a0[0].x, a0[0].y, a0[0].z, a0[0].w};
 #pragma unroll
@@ -674,14 +669,11 @@ extern "C" int zk_attn_decode(const void* q, const void* k_cache, const void* vt
     return 0;
 }
 
-#ifndef ZK_ATT_PRE
-#define ZK_ATT_PRE 1               // fused decode attention: in_proj slab loads before the key blocks (attn_common.h)
-#endif
 // the fused decode attention instantiation: RoPE form, non-temporal KV loads, in-launch combine, and the
 // slab pre-load form when the in_proj GEMM ran with exactly 4 splits (every c3-c5 decode step)
 template <bool COMB>
 static auto fused_attn_kernel(bool neox, bool kvnt, int gemm_nsplit) {
-    const bool pre = ZK_ATT_PRE && gemm_nsplit == 4;
+    const bool pre = gemm_nsplit == 4;
     if (pre)
         return neox ? (kvnt ? k_attn_decode<true, true, true, COMB, 4> : k_attn_decode<true, true, false, COMB, 4>)
                     : (kvnt ? k_attn_decode<true, false, true, COMB, 4> : k_attn_decode<true, false, false, COMB, 4>);
@@ -702,11 +694,7 @@ extern "C" int zk_attn_decode_qkv(const float* part, int gemm_nsplit, const floa
     ZK_REQUIRE(part != nullptr && freqs != nullptr && gemm_nsplit >= 1 && gemm_nsplit <= AT_MAXGS,
                "zk_attn_decode_qkv: bad arguments (gemm_nsplit=%d, max %d)", gemm_nsplit, AT_MAXGS);
     const float scale = 1.0f / sqrtf((float)hd);
-#ifdef ZK_ATT_DBGQ
-    const bf16_t* dbgq = (const bf16_t*)work;
-#else
     const bf16_t* dbgq = nullptr;
-#endif
     const bool kvnt = (double)R * Hkv * Smax * hd * 4 >= KV_NT_BYTES;
     auto kern = fused_attn_kernel<false>(rope_neox, kvnt, gemm_nsplit);
     hipLaunchKernelGGL(kern, dim3(nsplit, Hkv, R), dim3(256), 0, (hipStream_t)stream, dbgq, (bf16_t*)k_cache,

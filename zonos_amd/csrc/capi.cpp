@@ -126,19 +126,10 @@ extern "C" int zk_event_destroy(void* ev) {
     } while (0)
 
 // L2 warm-up descriptor of the decode GEMM zk_gemm_bf16(M, N, K, nsplit) (2 chunks per wave:
-// profiles/r3_l2_warm_micro.txt); ZK_L2_WARM=0 builds the step without it (A/B)
-#ifndef ZK_L2_WARM
-#define ZK_L2_WARM 1
-#endif
+// profiles/r3_l2_warm_micro.txt)
 static ZkWarm warm_desc(const void* W, int M, int N, int K, int nsplit, int mode = 0) {
-    return ZK_L2_WARM ? zk_gemm_warm_desc(W, M, N, K, nsplit, mode, 2) : ZkWarm{nullptr, 0, 0, 0, 0};
+    return zk_gemm_warm_desc(W, M, N, K, nsplit, mode, 2);
 }
-
-// B = 1: RoPE + KV write in the in_proj epilogue and the prologue-free attention (round 6);
-// ZK_B1_QKV_EPI=0 builds the round-5 sequence (in_proj slab -> fused-prologue attention) for A/Bs
-#ifndef ZK_B1_QKV_EPI
-#define ZK_B1_QKV_EPI 1
-#endif
 
 extern "C" int zk_decode_step(const zk_step_desc* d, void* stream) {
     if (d == nullptr || d->layers == nullptr || d->n_layer <= 0 || d->B <= 0) {
@@ -159,7 +150,7 @@ extern "C" int zk_decode_step(const zk_step_desc* d, void* stream) {
                            d->small ? nullptr : d->xn, skip, stream));
     for (int i = 0; i < d->n_layer; ++i) {
         const zk_step_layer& L = d->layers[i];
-        if (ZK_B1_QKV_EPI && d->small && d->attn_merge > 0 && !d->rope_neox) {
+        if (d->small && d->attn_merge > 0 && !d->rope_neox) {
             // B = 1: RoPE + KV write in the in_proj epilogue, a prologue-free attention over 32-key
             // slices, its partials merged by the out_proj GEMV
             ZK_STEP(zk_gemv_qkv_rope(d->x, L.wqkv, R, H, Hk, hd, L.ln1_w, L.ln1_b, d->eps, d->y, L.k_cache,

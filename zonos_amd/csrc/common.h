@@ -69,9 +69,6 @@ ZK_DEV uint4 pack8(const float* f) {
 }
 
 // ---------------------------------------------------------------- decode GEMM tile order
-#ifndef ZK_WS_XCD
-#define ZK_WS_XCD 1                // k_gemm_ws: XCD-aware split-major tile order
-#endif
 // Tile (bx, bz) of linear workgroup id L (= blockIdx.x + gx * blockIdx.z) of a k_gemm_ws grid
 // gx x 1 x gz. XCD-aware order: workgroups are dispatched round-robin over the 8 XCDs (L % 8),
 // and every workgroup of one K split reads the same activation slice. Numbering the work
@@ -79,7 +76,7 @@ ZK_DEV uint4 pack8(const float* f) {
 // split (in_proj / out_proj: 4) on each XCD, so its L2 fetches only that K slice of the activation
 // instead of all of it. Placement only: every tile computes the same numbers.
 ZK_DEV void ws_tile(int L, int gx, int gz, int& bx, int& bz) {
-    if (ZK_WS_XCD && gz > 1 && ((gx * gz) & 7) == 0) {
+    if (gz > 1 && ((gx * gz) & 7) == 0) {
         const int I = (L & 7) * ((gx * gz) >> 3) + (L >> 3);
         bz = I / gx;
         bx = I - bz * gx;

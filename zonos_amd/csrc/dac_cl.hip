@@ -96,12 +96,6 @@ __device__ uint32_t g_clhw[4096][8];       // every workgroup < 4096: HW_ID of w
 #else
 #define ZK_CL_STAMP(role, st) do { } while (0)
 #endif
-#ifndef ZK_CL_DIAG_NOW             // diagnostic builds only: weight slices loaded once (stale data)
-#define ZK_CL_DIAG_NOW 0
-#endif
-#ifndef ZK_CL_DIAG_NOMFMA          // diagnostic builds only: no MFMAs (wrong results)
-#define ZK_CL_DIAG_NOMFMA 0
-#endif
 constexpr int CL_DA = ZK_CL_DA;          // weight slices in flight ahead of the step being computed
 constexpr int CL_NW = CL_DA + 2;         // weight ring slots
 #ifndef ZK_CL_NLD
@@ -124,17 +118,8 @@ constexpr int CL_THREADS = 256 + 64 * CL_NLD;   // 4 compute waves + the loaders
 // registers are sized for
 // NWY: position waves (2 compute waves per position range: the two channel halves), NLDK loader
 // waves: 2 x NWY + NLDK waves per workgroup.
-// SPB: steps published per barrier -- the compute waves multiply SPB (tap, chunk) steps between two
-// barriers (a step is only FM x NQ MFMAs per wave, so a barrier per step holds the waves at the
-// barrier and the LDS read restart for a large share of the step); the rings hold 2 (SPB - 1) more
-// weight slots and the window ring ceil((DX + 2 SPB - 1) / ks) + 1 slots.
-#ifndef ZK_CL_SPB
-#define ZK_CL_SPB 1
-#endif
-constexpr int CL_SPB = ZK_CL_SPB;
-#ifndef ZK_RU_XPD
-#define ZK_RU_XPD 4                  // fused unit: residual output blocks in flight in the epilogue
-#endif
+// One step is published per barrier; the window ring holds ceil((DX + 1) / ks) + 1 slots.
+constexpr int RU_XPD = 4;            // fused unit: residual output blocks in flight in the epilogue
 // NWM: channel waves (2: the two channel halves; 1: every wave holds all CO_T channels of its
 // positions). FUSE (NWM = 1, one channel tile = all C channels): a whole residual unit in one
 // launch -- the k7 conv's accumulators, Snake'd to fp16, are already the B operands of
@@ -143,11 +128,8 @@ constexpr int CL_SPB = ZK_CL_SPB;
 // and writes x and the next Snake: the fp16 intermediate never goes to HBM (4 of the unit's 16 B
 // per element) and the 1x1 conv's launch, rings and barriers are gone.
 template <int FM, bool SF32, bool RES, int NQ, int DA = CL_DA, int OCC = 2, int NWY = 2, int NLDK = CL_NLD,
-          int SPB = CL_SPB, int NWM = 2, bool FUSE = false>
-#ifndef ZK_CL_LBW
-#define ZK_CL_LBW(OCC_, NT_) ((OCC_ * (NT_) + 255) / 256)
-#endif
-__global__ __launch_bounds__(64 * (NWM * NWY + NLDK), ZK_CL_LBW(OCC, 64 * (NWM * NWY + NLDK))) void k_conv_cl(
+          int NWM = 2, bool FUSE = false>
+__global__ __launch_bounds__(64 * (NWM * NWY + NLDK), (OCC * 64 * (NWM * NWY + NLDK) + 255) / 256) void k_conv_cl(
     const uint16_t* __restrict__ in, int Cin, int Tin, const uint16_t* __restrict__ w, long wphase,
     const float* __restrict__ bias, int Cout, int ks, int dil, int pad, int Qn, int nphase, int out_stride,
     int out_off0, int Tout, const float* resid, float* xout, const float* __restrict__ alpha,
@@ -190,9 +172,9 @@ __global__ __launch_bounds__(64 * (NWM * NWY + NLDK), ZK_CL_LBW(OCC, 64 * (NWM *
     const int win = QTT + (ks - 1) * dil;
     const int nxp = (win + 15) >> 4;             // window pieces (16 rows each)
     const int XS = nxp * 1024;
-    // weight ring slots: the loader refills a slot at most 2 SPB steps after the barrier that let it
-    // run (it can be SPB steps ahead of the barrier it passed, the compute waves SPB behind it)
-    constexpr int NWS = DA + 2 * SPB;
+    // weight ring slots: the loader refills a slot at most 2 steps after the barrier that let it
+    // run (it can be one step ahead of the barrier it passed, the compute waves one behind it)
+    constexpr int NWS = DA + 2;
     char* const wring = smem;
     char* const xring = smem + NWS * WS;
     const int nchunk = Cin / CI, nstep = nchunk * ks;
@@ -286,18 +268,15 @@ __global__ __launch_bounds__(64 * (NWM * NWY + NLDK), ZK_CL_LBW(OCC, 64 * (NWM *
                 }
             }
             if (j + DA >= 0 && iw < nt) {
-                if (!ZK_CL_DIAG_NOW || j + DA < DA + 2) {     // (diag: each weight slot filled once)
-                    char* dst = wring + wslot * WS;
-                    const uint16_t* src = wsrc0 + tw * wtap + cw * CI;
+                char* dst = wring + wslot * WS;
+                const uint16_t* src = wsrc0 + tw * wtap + cw * CI;
 #pragma unroll
-                    for (int pp = 0; pp < (NWP + NLDK - 1) / NLDK; ++pp) {
-                        const int p = pp * NLDK + lw;
-                        if (p >= NWP) break;
-                        __builtin_amdgcn_global_load_lds((const void*)(src + p * prs), (void*)(dst + p * 1024), 16, 0,
-                                                         0);
-                    }
-                    nl += nwl;
+                for (int pp = 0; pp < (NWP + NLDK - 1) / NLDK; ++pp) {
+                    const int p = pp * NLDK + lw;
+                    if (p >= NWP) break;
+                    __builtin_amdgcn_global_load_lds((const void*)(src + p * prs), (void*)(dst + p * 1024), 16, 0, 0);
                 }
+                nl += nwl;
                 if (++wslot == NWS) wslot = 0;
                 if (++tw == ks) {
                     tw = 0;
@@ -310,7 +289,7 @@ __global__ __launch_bounds__(64 * (NWM * NWY + NLDK), ZK_CL_LBW(OCC, 64 * (NWM *
 #pragma unroll
             for (int k = 0; k < DA; ++k) hist[k] = hist[k + 1];
             hist[DA] = nl;
-            if (j >= 0 && (j % SPB == SPB - 1 || j == total - 1)) {
+            if (j >= 0) {
                 // steps up to j need W(j), issued by iteration j - DA; everything issued later may stay in flight
                 int pend = 0;
 #pragma unroll
@@ -385,10 +364,8 @@ __global__ __launch_bounds__(64 * (NWM * NWY + NLDK), ZK_CL_LBW(OCC, 64 * (NWM *
         }
 
         for (int s = 0; s < nstep; ++s) {
-            if (SPB == 1 || (it * nstep + s) % SPB == 0) {
-                __builtin_amdgcn_s_barrier();        // steps s .. s + SPB - 1 are in LDS
-                asm volatile("" ::: "memory");
-            }
+            __builtin_amdgcn_s_barrier();            // step s is in LDS
+            asm volatile("" ::: "memory");
             if (wv == 0 && it == 0) ZK_CL_STAMP(2, s);
 #ifdef ZK_CL_PROF
             if (it == 0 && s == 0 && wv == 0 && blockIdx.x < 64 && lane == 0)
@@ -404,19 +381,11 @@ __global__ __launch_bounds__(64 * (NWM * NWY + NLDK), ZK_CL_LBW(OCC, 64 * (NWM *
 #pragma unroll
             for (int n = 0; n < NQ; ++n)
                 bq[n] = *reinterpret_cast<const uint4*>(xb + I::off(wn * 16 * NQ + n * 16 + ln + t * dil, lg));
-            if (ZK_CL_DIAG_NOMFMA) {          // diag: keep the operand reads, drop the MFMAs
 #pragma unroll
-                for (int m = 0; m < FM; ++m)
+            for (int m = 0; m < FM; ++m)
 #pragma unroll
-                    for (int n = 0; n < NQ; ++n) acc[m][n][0] += __uint_as_float(a[m].x ^ bq[n].y);
-            } else {
-#pragma unroll
-                for (int m = 0; m < FM; ++m)
-#pragma unroll
-                    for (int n = 0; n < NQ; ++n)
-                        acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(as_h8(a[m]), as_h8(bq[n]), acc[m][n], 0, 0,
-                                                                           0);
-            }
+                for (int n = 0; n < NQ; ++n)
+                    acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(as_h8(a[m]), as_h8(bq[n]), acc[m][n], 0, 0, 0);
             if (++t == ks) {
                 t = 0;
                 if (++xslot == nx_slots) xslot = 0;
@@ -456,7 +425,7 @@ __global__ __launch_bounds__(64 * (NWM * NWY + NLDK), ZK_CL_LBW(OCC, 64 * (NWM *
             // one block ahead of the block being multiplied
             // (XPD output blocks of residual rows in flight: the accumulators are packed into h by now,
             // so their registers hold the prefetch)
-            constexpr int XPD = ZK_RU_XPD < FM ? ZK_RU_XPD : FM;
+            constexpr int XPD = RU_XPD < FM ? RU_XPD : FM;
             float4 xr[XPD][NQ];
             auto load_x = [&](int mo, int buf) {
 #pragma unroll
@@ -617,13 +586,7 @@ __global__ __launch_bounds__(256) void k_rvq_cl(const int64_t* __restrict__ code
 // by whole float4 loads (row stride C + 4 floats: the 16 lanes of a ds_read_b128 hit distinct
 // banks), then each thread sums its position's 7 x C products in the order k, c, in four chains
 // (c mod 4) added at the end.
-#ifndef ZK_TAIL_T
-#define ZK_TAIL_T 128
-#endif
-#ifndef ZK_TAIL_NB
-#define ZK_TAIL_NB 16
-#endif
-constexpr int TAIL_T = ZK_TAIL_T;    // positions (threads) per workgroup
+constexpr int TAIL_T = 128;          // positions (threads) per workgroup
 __global__ __launch_bounds__(TAIL_T) void k_tail_cl(const float* __restrict__ s, int C, int T,
                                                     const float* __restrict__ w, const float* __restrict__ bias,
                                                     float* __restrict__ out, const int32_t* __restrict__ lens,
@@ -643,7 +606,7 @@ __global__ __launch_bounds__(TAIL_T) void k_tail_cl(const float* __restrict__ s,
     // staging in batches of TAIL_NB loads per thread, all issued before the first LDS store: one
     // load in flight per thread (load -> store -> next load) made the kernel a chain of ~25 memory
     // round trips per workgroup (1.3 TB/s)
-    constexpr int TAIL_NB = ZK_TAIL_NB;
+    constexpr int TAIL_NB = 16;
     for (int i0 = threadIdx.x; i0 < total; i0 += TAIL_T * TAIL_NB) {
         float4 v[TAIL_NB];
 #pragma unroll
@@ -836,36 +799,29 @@ int launch_conv(long ntiles, size_t lds, hipStream_t st, const uint16_t* in, int
 }
 
 // The fused residual unit: position waves each holding all C channels (C = 96: 64 positions,
-// FM = 6, NQ = 4; C = 192: 32 positions, FM = 12, NQ = 2), persistent like launch_conv. ZK_RU_OCC
-// (C = 96) 1: one workgroup per CU of 8 position waves + 4 loaders, the 1x1 weights in LDS; 2: two
-// workgroups per CU of 4 position waves + 2 loaders, the 1x1 weights read through L1. C = 192: one
-// workgroup per CU of 8 position waves (256-position tiles) + 4 loaders, the 1x1 weights (72 KB)
-// read from L2 one output block ahead.
-#ifndef ZK_RU_OCC
-#define ZK_RU_OCC 1
-#endif
-#ifndef ZK_DAC_FUSE192
-#define ZK_DAC_FUSE192 0             // C = 192 fused: 11.6 ms per unit vs 10.9 for the pair
-#endif
+// FM = 6, NQ = 4; C = 192: 32 positions, FM = 12, NQ = 2), persistent like launch_conv.
+// C = 96: one workgroup per CU of 8 position waves + 4 loaders, the 1x1 weights in LDS (two workgroups
+// per CU of 4 position waves + 2 loaders, the weights read through L1, measured slower: DESIGN.md §6
+// round 4). C = 192: one workgroup per CU of 8 position waves (256-position tiles) + 4 loaders, the
+// 1x1 weights (72 KB) read from L2 one output block ahead.
 template <int C_, bool SF32>
 int launch_resunit(const uint16_t* s_in, int B, int T, const uint16_t* w7, const float* b7, int dil, const float* a2,
                    const uint16_t* w1, const float* b1, float* x, const float* alpha_next, void* s_out,
                    const int32_t* lens, int scale, hipStream_t st) {
-    constexpr int FM = C_ / 16, NQ = C_ == 96 ? 4 : 2, OCC = C_ == 96 ? ZK_RU_OCC : 1;
-    constexpr int NWY = OCC == 1 ? 8 : 4, NLD = OCC == 1 ? 4 : 2;
+    constexpr int FM = C_ / 16, NQ = C_ == 96 ? 4 : 2, NWY = 8, NLD = 4;
     constexpr int NT = 64 * (NWY + NLD);
     constexpr int qt = 16 * NQ * NWY;
-    constexpr bool w1lds = OCC == 1 && C_ * (C_ + 8) * 2 <= 24 * 1024;     // = the kernel's W1LDS
-    auto kern = &k_conv_cl<FM, SF32, false, NQ, CL_DA, OCC, NWY, NLD, CL_SPB, 1, true>;
+    constexpr bool w1lds = C_ * (C_ + 8) * 2 <= 24 * 1024;     // = the kernel's W1LDS
+    auto kern = &k_conv_cl<FM, SF32, false, NQ, CL_DA, 1, NWY, NLD, 1, true>;
     const int ks = 7, win = qt + (ks - 1) * dil;
     const size_t xs = (size_t)((win + 15) / 16) * 1024, ws = (size_t)C_ * 64;
     const size_t fixed = (size_t)2 * 6 * C_ * sizeof(float) + (w1lds ? (size_t)C_ * (C_ + 8) * 2 : 0);
-    const size_t cap = OCC == 1 ? 160 * 1024 : 80 * 1024;
-    const int spb = CL_SPB, nws = CL_DA + 2 * spb;
-    int dx = std::max(CL_DA, ks), nx = 1 + (dx + 2 * spb - 1 + ks - 1) / ks;
+    const size_t cap = 160 * 1024;
+    const int nws = CL_DA + 2;
+    int dx = std::max(CL_DA, ks), nx = 1 + (dx + ks) / ks;
     while (dx > CL_DA && nws * ws + nx * xs + fixed > cap) {
         --dx;
-        nx = 1 + (dx + 2 * spb - 1 + ks - 1) / ks;
+        nx = 1 + (dx + ks) / ks;
     }
     const size_t lds = nws * ws + nx * xs + fixed;
     ZK_REQUIRE(lds <= cap, "zk_dac_resunit_cl: LDS %zu too large (C %d dil %d)", lds, C_, dil);
@@ -938,39 +894,32 @@ extern "C" int zk_dac_conv_cl(const uint16_t* in, int B, int Cin, int Tin, const
     if (B == 0 || Qn <= 0) return 0;
     const int nco = Cout / 32;
     const int FM = nco % 4 == 0 ? 4 : (nco % 3 == 0 ? 3 : (nco % 2 == 0 ? 2 : 1));
-    // 256-position tiles for the plain convs without a residual at FM <= 3 (the 96-192-channel k7
-    // convs, overhead-bound at 128: -6 % / -15 %); the residual convs keep 128 (their prefetched
-    // residual tile would not fit the registers beside twice the accumulators), and so do the
-    // polyphase ConvTranspose convs (+12-22 % with 256, profiles/r1_dac_wide_tiles_ab.txt)
+    // Wider tiles for the plain convs without a residual at FM <= 3 (the 96-192-channel k7 convs,
+    // overhead-bound at 128 positions: -6 % / -15 % at 256); the residual convs keep 128 (their
+    // prefetched residual tile would not fit the registers beside twice the accumulators), and so do
+    // the polyphase ConvTranspose convs (+12-22 % with 256, profiles/r1_dac_wide_tiles_ab.txt)
     // (one workgroup per CU with a deeper weight ring measured slower: DESIGN.md §6)
-#ifndef ZK_CL_WIDE
-#define ZK_CL_WIDE 1
-#endif
-    const bool wide = ZK_CL_WIDE && resid == nullptr && !s_f32 && nphase == 1 && FM <= 3;
-    // fat: the wide convs as ONE workgroup per CU of 8 compute waves (2 channel halves x 4 position
+    // fat: those convs as ONE workgroup per CU of 8 compute waves (2 channel halves x 4 position
     // quarters, 512-position tiles) + 4 loaders = 12 waves, exactly 3 per SIMD. Two 6-wave
-    // workgroups per CU (the same compute per step) were co-resident only where the wave placement
+    // workgroups per CU of 256-position tiles (the same compute per step) were co-resident only where the wave placement
     // happened to balance the SIMDs (3 waves per SIMD is the register limit at 150 VGPRs): 1.3 per CU
     // on average (tools/dac_conv_stamps.py HW_ID census); one workgroup also shares each weight slice
     // among twice the waves.
-#ifndef ZK_CL_FAT
-#define ZK_CL_FAT 1
-#endif
-    const bool fat = ZK_CL_FAT && wide;
-    const int qt = fat ? 4 * QT : (wide ? 2 * QT : QT);
+    const bool fat = resid == nullptr && !s_f32 && nphase == 1 && FM <= 3;
+    const int qt = fat ? 4 * QT : QT;
     const int win = qt + (ks - 1) * dil;
     const size_t xs = (size_t)((win + 15) / 16) * 1024;
     const size_t ws = (size_t)32 * FM * 64;
     const int da = CL_DA;
     const size_t lds_cap = fat ? 160 * 1024 : 80 * 1024;
-    // window lead DX >= da steps, ring NX = 1 + ceil((DX + 2 SPB - 1)/ks) slots, weight ring da + 2 SPB;
+    // window lead DX >= da steps, ring NX = 1 + ceil((DX + 1)/ks) slots, weight ring da + 2;
     // keep LDS <= 80 KiB (2 per CU)
     const size_t ept = (size_t)2 * 3 * 32 * FM * sizeof(float);      // epilogue constants tables (x 2)
-    const int spb = CL_SPB, nws = da + 2 * spb;
-    int dx = std::max(da, ks), nx = 1 + (dx + 2 * spb - 1 + ks - 1) / ks;
+    const int nws = da + 2;
+    int dx = std::max(da, ks), nx = 1 + (dx + ks) / ks;
     while (dx > da && nws * ws + nx * xs + ept > lds_cap) {
         --dx;
-        nx = 1 + (dx + 2 * spb - 1 + ks - 1) / ks;
+        nx = 1 + (dx + ks) / ks;
     }
     const size_t lds = nws * ws + nx * xs + ept;
     ZK_REQUIRE(lds <= 160 * 1024, "zk_dac_conv_cl: LDS %zu too large", lds);
@@ -988,9 +937,9 @@ extern "C" int zk_dac_conv_cl(const uint16_t* in, int B, int Cin, int Tin, const
                                      s_f32, lens, in_scale, out_scale, nq, nx, dx)))
     switch (FM) {
         case 4: ZK_CL(4, 4); break;
-        case 3: if (fat) ZK_CLF(3); else if (wide) ZK_CL(3, 8); else ZK_CL(3, 4); break;
-        case 2: if (fat) ZK_CLF(2); else if (wide) ZK_CL(2, 8); else ZK_CL(2, 4); break;
-        default: if (fat) ZK_CLF(1); else if (wide) ZK_CL(1, 8); else ZK_CL(1, 4); break;
+        case 3: if (fat) ZK_CLF(3); else ZK_CL(3, 4); break;
+        case 2: if (fat) ZK_CLF(2); else ZK_CL(2, 4); break;
+        default: if (fat) ZK_CLF(1); else ZK_CL(1, 4); break;
     }
 #undef ZK_CLF
 #undef ZK_CL
@@ -998,14 +947,10 @@ extern "C" int zk_dac_conv_cl(const uint16_t* in, int B, int Cin, int Tin, const
     return 0;
 }
 
-// ZK_DAC_FUSE: 0 = every residual unit as two convs; 1 = the units of C = 96 fused except the last
-// (its fp32 Snake output makes the fused epilogue spill); 2 = the last one too
-#ifndef ZK_DAC_FUSE
-#define ZK_DAC_FUSE 1
-#endif
-extern "C" int zk_dac_resunit_supported(int C) {
-    return C == 96 ? ZK_DAC_FUSE : (C == 192 && ZK_DAC_FUSE192 ? ZK_DAC_FUSE : 0);
-}
+// 0 = the residual units of this width run as two convs; 1 = fused except the last (its fp32 Snake
+// output makes the fused epilogue spill). C = 192 fused measured slower (11.6 ms per unit vs 10.9 for
+// the pair: DESIGN.md §6 round 4); zk_dac_resunit_cl still takes it.
+extern "C" int zk_dac_resunit_supported(int C) { return C == 96 ? 1 : 0; }
 
 extern "C" int zk_dac_resunit_cl(const uint16_t* s_in, int B, int C, int T, const uint16_t* w7, const float* b7,
                                  int dil, const float* a2, const uint16_t* w1, const float* b1, float* x,

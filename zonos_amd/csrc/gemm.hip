@@ -33,34 +33,20 @@ constexpr int BM = 128, BN = 64, BK = 64, NT = 256;
 
 
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-// streamed-once weights: non-temporal 16-byte load (global_load_dwordx4 ... nt)
-template <bool NT_>
+// streamed-once weights (decode): non-temporal 16-byte load (global_load_dwordx4 ... nt)
 ZK_DEV uint4 ldg_w(const bf16_t* p) {
-    if constexpr (NT_) return __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p)));
-    else return *reinterpret_cast<const uint4*>(p);
+    return __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p)));
 }
 
-// Weight layout. ZK_W_PACKED: "fragment-packed" [N/16][K/32][64 lanes][8] -- the 16x32 B
+// Weight layout: "fragment-packed" [N/16][K/32][64 lanes][8] -- the 16x32 B
 // fragment of n-tile nt and k-slice kc is one contiguous 1 KB block in lane order, and a
 // tile's K-slices follow each other, so a wave streams its 16 weight rows as ONE sequential
 // run (each wave-instruction reads 1 KB contiguous instead of 16 rows x 64 B).
-// Otherwise nn.Linear row-major [N][K].
-#ifndef ZK_W_PACKED
-#define ZK_W_PACKED 1
-#endif
-#if ZK_W_PACKED
 constexpr int WCH = 1024;     // elements per 64-wide K chunk of one wave (2 fragments)
 constexpr int WHALF = 512;
-ZK_DEV const bf16_t* w_base(const bf16_t* W, int ntile_row0, int, int K, int kbeg, int lane) {
+ZK_DEV const bf16_t* w_base(const bf16_t* W, int ntile_row0, int K, int kbeg, int lane) {
     return W + ((size_t)(ntile_row0 >> 4) * (K >> 5) + (kbeg >> 5)) * 512 + lane * 8;
 }
-#else
-constexpr int WCH = BK;
-constexpr int WHALF = 32;
-ZK_DEV const bf16_t* w_base(const bf16_t* W, int, int row, int K, int kbeg, int lane) {
-    return W + (size_t)row * K + kbeg + (lane >> 4) * 8;
-}
-#endif
 
 // LDS byte offset of 16-byte chunk c (0..7) of tile row `row` (128-byte rows, XOR swizzle)
 ZK_DEV int lds_off(int row, int c) { return row * 128 + ((c ^ (row & 7)) << 4); }
@@ -68,7 +54,7 @@ ZK_DEV int lds_off(int row, int c) { return row * 128 + ((c ^ (row & 7)) << 4); 
 // NTW 16-column tiles per wave (tile 128 x 64*NTW): every activation fragment read from LDS
 // feeds NTW MFMAs -- with NTW = 1 the four waves' fragment reads (1 KB per MFMA each) exceed the
 // LDS array's 256 B/clk, with NTW = 2 the prefill GEMMs become MFMA-bound.
-template <int MODE, int U, bool WNT = false, int NTW = 1>
+template <int MODE, int U, int NTW = 1>
 __global__ __launch_bounds__(NT) void k_gemm(const bf16_t* __restrict__ A, long lda, const bf16_t* __restrict__ W,
                                              int M, int N, int K, int kslice, float* __restrict__ Cpart,
                                              bf16_t* __restrict__ Cout, const int32_t* skip) {
@@ -89,7 +75,7 @@ __global__ __launch_bounds__(NT) void k_gemm(const bf16_t* __restrict__ A, long 
         const int c0 = n0 + (w * NTW + t) * 16;
         wn[t] = c0 + ln;
         wvalid[t] = wn[t] < N;
-        wrow[t] = w_base(W, c0, wvalid[t] ? wn[t] : 0, K, kbeg, lane);
+        wrow[t] = w_base(W, c0, K, kbeg, lane);
     }
 
     // activation staging: 4 x 16 B per thread per K chunk (row = q>>3, 16-B chunk = q&7)
@@ -139,8 +125,8 @@ __global__ __launch_bounds__(NT) void k_gemm(const bf16_t* __restrict__ A, long 
         const int pc = min(p, nchunks - 1);
 #pragma unroll
         for (int t = 0; t < NTW; ++t) {
-            wr0[p][t] = ldg_w<WNT>(wrow[t] + pc * WCH);
-            wr1[p][t] = ldg_w<WNT>(wrow[t] + pc * WCH + WHALF);
+            wr0[p][t] = *reinterpret_cast<const uint4*>(wrow[t] + pc * WCH);
+            wr1[p][t] = *reinterpret_cast<const uint4*>(wrow[t] + pc * WCH + WHALF);
         }
     }
     ZK_LOAD_A(0);
@@ -155,8 +141,8 @@ __global__ __launch_bounds__(NT) void k_gemm(const bf16_t* __restrict__ A, long 
                 const int pc = min(ch + PF, nchunks - 1);
 #pragma unroll
                 for (int t = 0; t < NTW; ++t) {
-                    wr0[(u + PF) % U][t] = ldg_w<WNT>(wrow[t] + pc * WCH);
-                    wr1[(u + PF) % U][t] = ldg_w<WNT>(wrow[t] + pc * WCH + WHALF);
+                    wr0[(u + PF) % U][t] = *reinterpret_cast<const uint4*>(wrow[t] + pc * WCH);
+                    wr1[(u + PF) % U][t] = *reinterpret_cast<const uint4*>(wrow[t] + pc * WCH + WHALF);
                 }
             }
             const char* base = smem + (ch & 1) * (BM * BK * 2);
@@ -221,22 +207,12 @@ __global__ __launch_bounds__(NT) void k_gemm(const bf16_t* __restrict__ A, long 
 // (global_load_lds_dwordx4, DA chunks ahead, XOR swizzle applied on the source address), and
 // waves 0-3 only stream weights into a PF-chunk register ring; one raw s_barrier per chunk
 // publishes the next activation chunk (it does not drain VMEM).
-#ifndef ZK_WS_NB
-#define ZK_WS_NB 6
-#define ZK_WS_DA 4
-#define ZK_WS_OCC 1
-#endif
-constexpr int WS_NB = ZK_WS_NB;  // LDS ring slots (16 KB each)
-constexpr int WS_DA = ZK_WS_DA;  // activation chunks in flight (loader); WS_NB >= WS_DA + 2
-#ifndef ZK_WS_NLD
-#define ZK_WS_NLD 4
-#endif
-constexpr int WS_NLD = ZK_WS_NLD;            // loader waves (each moves 1/WS_NLD of every chunk)
+constexpr int WS_NB = 6;         // LDS ring slots (16 KB each)
+constexpr int WS_DA = 4;         // activation chunks in flight (loader); WS_NB >= WS_DA + 2
+constexpr int WS_OCC = 1;        // workgroups per CU the kernel is sized for
+constexpr int WS_NLD = 4;        // loader waves (each moves 1/WS_NLD of every chunk)
 #ifndef ZK_WS_PF
 #define ZK_WS_PF 4
-#endif
-#ifndef ZK_WS_NT
-#define ZK_WS_NT 1
 #endif
 constexpr int WS_LDSPF = 1;      // chunks published ahead of the one being multiplied
 constexpr int WS_PF = ZK_WS_PF;  // weight chunks in flight per compute wave: the SwiGLU fc1 (mode 1)
@@ -245,28 +221,11 @@ constexpr int WS_PF = ZK_WS_PF;  // weight chunks in flight per compute wave: th
 #endif
 constexpr int WS_PF0 = ZK_WS_PF0; // ... and the split-K slab GEMMs (mode 0): 3 measured faster for the
                                   // in_proj / out_proj / fc2 shapes, 4 for fc1 (profiles/r3s2_gemm_pf_ab.txt)
-constexpr bool WS_NT = ZK_WS_NT; // non-temporal weight loads
-#ifndef ZK_WS_DEFER
-#define ZK_WS_DEFER 0              // k_gemm_ws: step word tested after the first loads (A/B only)
-#endif
 
-
-// k_gemm_ws split-K slab stores (read once by the consumer kernel): non-temporal with ZK_SLAB_NT
+// k_gemm_ws split-K slab stores (read once by the consumer kernel) are non-temporal
 // (B=64: decode step 3.928 vs 3.959 ms; the B <= 8 GEMV keeps plain stores: its slabs are small
 // and nt cost 2.5 % per step at B=1)
-#ifndef ZK_SLAB_NT
-#define ZK_SLAB_NT 1
-#endif
-#ifndef ZK_SLAB_SC1
-#define ZK_SLAB_SC1 0              // write-through (sc1) slab stores: nothing left dirty in L2 at the boundary
-#endif
-#ifndef ZK_WS_EPI
-#define ZK_WS_EPI 1                // k_gemm_ws epilogue staged through LDS (whole-row stores)
-#endif
-ZK_DEV void st_slab(float* p, float v) {
-    if constexpr (ZK_SLAB_NT) __builtin_nontemporal_store(v, p);
-    else *p = v;
-}
+ZK_DEV void st_slab(float* p, float v) { __builtin_nontemporal_store(v, p); }
 
 template <int N_>
 ZK_DEV void vm_wait() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N_) : "memory"); }
@@ -274,8 +233,9 @@ ZK_DEV void vm_wait() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N_) : "memory")
 // MT = 16-row M tiles actually present (1, 2, 4, 8): small batches stage and multiply only
 // the rows they have (B = 1 decode: 2 rows -> one 16-row tile instead of 8).
 // NG = 16-column groups per compute wave: every activation fragment read from LDS feeds NG MFMAs,
-// and a workgroup covers 16 * NCW * NG columns, so a wider tile stages the same activation once
-// for NG times the weights (LDS reads and per-CU activation intake per weight byte / NG).
+// and a workgroup covers 16 * NCW * NG columns. Every launch uses NG = 1 (NG = 2 measured slower for
+// both modes and is no longer instantiated); the parameter stays because writing the kernel without
+// it changes hipcc's register allocation and block order in every instantiation.
 // NB = activation fragment buffers (2: the next chunk's fragments are read while this one is
 // multiplied).
 // Loader waves: WS_NLD, fewer when that would put a ninth wave (a third per SIMD: 168 VGPRs) in the
@@ -290,7 +250,7 @@ constexpr int ws_nld() {
     return n;
 }
 template <int MODE, int NCH, int PF, int MT, int NCW = 4, int NG = 1, int NB = (NCW > 5 ? 1 : 2)>
-__global__ __launch_bounds__(64 * (NCW + ws_nld<NCW, MT>()), ZK_WS_OCC) void k_gemm_ws(const bf16_t* __restrict__ A, long lda,
+__global__ __launch_bounds__(64 * (NCW + ws_nld<NCW, MT>()), WS_OCC) void k_gemm_ws(const bf16_t* __restrict__ A, long lda,
                                                            const bf16_t* __restrict__ W, int M, int N, int K,
                                                            int kslice, float* __restrict__ Cpart,
                                                            bf16_t* __restrict__ Cout, const int32_t* skip,
@@ -300,9 +260,8 @@ __global__ __launch_bounds__(64 * (NCW + ws_nld<NCW, MT>()), ZK_WS_OCC) void k_g
     // (the skip word is tested first here: deferring the test behind the first loads, as k_gemv_f
     // does, measured 0.3-1.2 % slower per c3 step with a vector or a scalar load of the word,
     // profiles/r3s2_skip_defer_ab.txt; again in round 6, 3.500-3.510 vs 3.473-3.489 ms, while k_resid_ln gained:
-    // profiles/r6_c3_gemm_ws_defer_ab.txt; ZK_WS_DEFER=1 builds that form)
-    if (!ZK_WS_DEFER)
-        if (skip && *skip) return;
+    // profiles/r6_c3_gemm_ws_defer_ab.txt)
+    if (skip && *skip) return;
     int bx, bz;
     ws_tile(blockIdx.x + gridDim.x * blockIdx.z, gridDim.x, gridDim.z, bx, bz);     // gridDim.y == 1
     constexpr int BNW = 16 * NCW * NG;            // columns per workgroup
@@ -333,21 +292,11 @@ __global__ __launch_bounds__(64 * (NCW + ws_nld<NCW, MT>()), ZK_WS_OCC) void k_g
                 const int row = 8 * i + rl;
                 const int m = min(row, M - 1);
                 const bf16_t* src = A + (size_t)m * lda + k0 + ((sl ^ (row & 7)) << 3);
-#ifndef ZK_DBG_NOALOAD
                 __builtin_amdgcn_global_load_lds((const void*)src, (void*)(dst + i * 1024), 16, 0, 0);
-#else
-                (void)src; (void)dst;
-#endif
             }
         };
         const int pre = min(WS_DA, nchunks);
         for (int c = 0; c < pre; ++c) issue(c);
-        if constexpr (ZK_WS_DEFER) {
-            if (ld_word_here(skip)) {           // the LDS-DMA writes land before the workgroup may leave
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                return;
-            }
-        }
         for (int c = 0; c < nchunks; ++c) {
             // barrier c publishes chunk `need` (one chunk ahead, so the compute
             // waves can read chunk c+1's fragments while they multiply chunk c)
@@ -370,7 +319,7 @@ __global__ __launch_bounds__(64 * (NCW + ws_nld<NCW, MT>()), ZK_WS_OCC) void k_g
             // two __syncthreads must not wait for these loads
             warm_units(wW, wK, wgx, wgz, wch, blockIdx.x + gridDim.x * blockIdx.z, gridDim.x * gridDim.z, ld, NLD,
                        lane, smem + WS_NB * (MT * 16 * BK * 2));
-            if (ZK_WS_EPI && (MODE == 1 || N % 4 == 0)) {
+            if (MODE == 1 || N % 4 == 0) {
                 __builtin_amdgcn_s_barrier();
                 __builtin_amdgcn_s_barrier();
             }
@@ -386,7 +335,7 @@ __global__ __launch_bounds__(64 * (NCW + ws_nld<NCW, MT>()), ZK_WS_OCC) void k_g
         const int c0 = n0 + (w * NG + g) * 16;
         // a 16-row tile wholly past N streams tile 0 (never stored): the packed image ends at ceil64(N)
         const int trow = c0 < N ? c0 : 0;
-        wrow[g] = w_base(W, trow, c0 + ln < N ? c0 + ln : 0, K, kbeg, lane);
+        wrow[g] = w_base(W, trow, K, kbeg, lane);
     }
     f32x4 acc[NG][MT];
 #pragma unroll
@@ -403,20 +352,8 @@ __global__ __launch_bounds__(64 * (NCW + ws_nld<NCW, MT>()), ZK_WS_OCC) void k_g
         const int pc = p < NCH ? p : NCH - 1;
 #pragma unroll
         for (int g = 0; g < NG; ++g) {
-            wr0[g][p] = ldg_w<WS_NT>(wrow[g] + pc * WCH);
-            wr1[g][p] = ldg_w<WS_NT>(wrow[g] + pc * WCH + WHALF);
-        }
-    }
-    if constexpr (ZK_WS_DEFER) {
-        if (ld_word_here(skip)) {
-#pragma unroll
-            for (int p = 0; p < PF; ++p)
-#pragma unroll
-                for (int g = 0; g < NG; ++g) {
-                    keep_live(wr0[g][p]);
-                    keep_live(wr1[g][p]);
-                }
-            return;
+            wr0[g][p] = ldg_w(wrow[g] + pc * WCH);
+            wr1[g][p] = ldg_w(wrow[g] + pc * WCH + WHALF);
         }
     }
     // activation fragments of the next chunk are read from LDS (register double buffer) while
@@ -439,8 +376,8 @@ __global__ __launch_bounds__(64 * (NCW + ws_nld<NCW, MT>()), ZK_WS_OCC) void k_g
         if (ch + PF < NCH) {
 #pragma unroll
             for (int g = 0; g < NG; ++g) {
-                wr0[g][(ch + PF) % U] = ldg_w<WS_NT>(wrow[g] + (ch + PF) * WCH);
-                wr1[g][(ch + PF) % U] = ldg_w<WS_NT>(wrow[g] + (ch + PF) * WCH + WHALF);
+                wr0[g][(ch + PF) % U] = ldg_w(wrow[g] + (ch + PF) * WCH);
+                wr1[g][(ch + PF) % U] = ldg_w(wrow[g] + (ch + PF) * WCH + WHALF);
             }
         }
         if (NB == 2 && ch + 1 < NCH) {
@@ -467,7 +404,7 @@ __global__ __launch_bounds__(64 * (NCW + ws_nld<NCW, MT>()), ZK_WS_OCC) void k_g
             read_frags(ch + 1, 0);
         }
     }
-    if (ZK_WS_EPI && (MODE == 1 || N % 4 == 0)) {
+    if (MODE == 1 || N % 4 == 0) {
         // Epilogue staged through the (now idle) LDS ring so that every store instruction writes
         // whole rows: slabs of BNW floats per row (full 128-B lines) instead of 64-B pieces, SwiGLU
         // rows of BNW / 2 bf16 instead of 16-B pieces. (The loader waves have exited; a workgroup
@@ -500,10 +437,7 @@ __global__ __launch_bounds__(64 * (NCW + ws_nld<NCW, MT>()), ZK_WS_OCC) void k_g
                     const f32x4 v = *reinterpret_cast<const f32x4*>(tile + m * TS + c4);
                     float* dst = C + (size_t)m * N + n0 + c4;
                     if (n0 + c4 + 3 < N) {
-                        if constexpr (ZK_SLAB_SC1)
-                            asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(dst), "v"(v) : "memory");
-                        else if constexpr (ZK_SLAB_NT) __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(dst));
-                        else *reinterpret_cast<f32x4*>(dst) = v;
+                        __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(dst));
                     } else {
                         for (int e = 0; e < 4 && n0 + c4 + e < N; ++e) dst[e] = v[e];
                     }
@@ -533,6 +467,7 @@ __global__ __launch_bounds__(64 * (NCW + ws_nld<NCW, MT>()), ZK_WS_OCC) void k_g
         }
         return;
     }
+    // slabs whose N is no multiple of 4 (the heads GEMM, N = 9234): stores straight from the registers
 #pragma unroll
     for (int g = 0; g < NG; ++g) {
         const int wn = n0 + (w * NG + g) * 16 + ln;
@@ -547,21 +482,6 @@ __global__ __launch_bounds__(64 * (NCW + ws_nld<NCW, MT>()), ZK_WS_OCC) void k_g
                         if (m < M) st_slab(C + (size_t)m * N + wn, acc[g][mt][i]);
                     }
             }
-        } else {
-            const int F = N / 2;
-            const int f = (n0 + (w * NG + g) * 16) / 2 + (ln & 7);
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const float mine = round_bf(acc[g][mt][i]);
-                    const float other = __shfl_xor(mine, 8, 64);
-                    const int m = mt * 16 + lg * 4 + i;
-                    if (ln < 8 && m < M && f < F) {
-                        const float sl = round_bf(other / (1.0f + expf(-other)));
-                        Cout[(size_t)m * F + f] = f2bf(mine * sl);
-                    }
-                }
         }
     }
 }
@@ -599,7 +519,7 @@ __global__ __launch_bounds__(256, 1) void k_gemv_rk(const bf16_t* __restrict__ A
     uint4 wr[U][NTW], ar[U];
     auto issue = [&](int st, int slot) {
 #pragma unroll
-        for (int t = 0; t < NTW; ++t) wr[slot][t] = ldg_w<true>(wp[t] + st * 512);
+        for (int t = 0; t < NTW; ++t) wr[slot][t] = ldg_w(wp[t] + st * 512);
         ar[slot] = *reinterpret_cast<const uint4*>(ap + st * 32);
     };
 #pragma unroll
@@ -715,21 +635,12 @@ constexpr int GF_AT_G = AT_G, GF_AT_STR = AT_STR;    // the partials layout of a
 static_assert(GF_AT_STR == 2 * GF_AT_G + GF_AT_G * 128, "attention partials layout");
 // XR: rows the LDS activation image holds (2 for B = 1, 16 otherwise): a 16-row image is 66 KB and
 // caps the LayerNorm-prologue GEMVs at 2 workgroups per CU; the 2-row image (8 KB) does not.
-// XC (ZK_GF_XC, B = 1 GEMVs without a LayerNorm or merge prologue: fc2): the activation rows are copied
+// XC (B = 1 GEMVs without a LayerNorm or merge prologue: fc2): the activation rows are copied
 // into the LDS image once per wave -- each wave its own K range, 4 x 16 B per lane at K = 8192 -- instead
 // of being re-loaded from L2 beside every weight load (two 16-B-per-lane loads per weight piece, 16 lanes
 // per row for the 2 real rows: 2/3 of the wave's load instructions). Same operands, same MFMA order:
 // bit-identical. A pure-stream probe of the fc2 shape: 6.45 -> 7.01 us per launch with those loads
 // (profiles/r6_stream_order_probe.txt).
-#ifndef ZK_GF_XC
-#define ZK_GF_XC 1
-#endif
-#ifndef ZK_GF_LNW
-#define ZK_GF_LNW 1
-#endif
-#ifndef ZK_GF_OCC2
-#define ZK_GF_OCC2 1               // min waves per SIMD the B = 1 (XR = 2) instantiations are sized for
-#endif
 // mode 3 (in_proj of the B = 1 step): the epilogue of the decode attention's old prologue. The GEMV
 // output is final (no split-K), so each column pair (2j, 2j+1) of a q / k head -- two neighbouring lanes
 // of one 16-column tile -- is rounded to bf16 and rotated here (interleaved RoPE, _torch.py:18-30, the
@@ -745,7 +656,7 @@ struct GfQkv {
 };
 
 template <int MODE, bool LN, int NTW, bool HALF, int NW, int KS, int PF, int MRG = 0, int XR = 16>
-__global__ __launch_bounds__(64 * NW, XR == 2 ? ZK_GF_OCC2 : 1) void k_gemv_f(const bf16_t* __restrict__ A, long lda,
+__global__ __launch_bounds__(64 * NW, 1) void k_gemv_f(const bf16_t* __restrict__ A, long lda,
                                                        const bf16_t* __restrict__ W, int M, int N, int K,
                                                        const bf16_t* __restrict__ lnw, const bf16_t* __restrict__ lnb,
                                                        float eps, float* __restrict__ Cf, bf16_t* __restrict__ Cb,
@@ -757,7 +668,7 @@ __global__ __launch_bounds__(64 * NW, XR == 2 ? ZK_GF_OCC2 : 1) void k_gemv_f(co
     static_assert(!LN || KS * NW * 32 == 2048, "LN prologue: K = 2048");
     static_assert(!MRG || (!LN && NW == 8 && KS * NW * 32 == 2048), "merge prologue: K = 2048, 8 waves");
     static_assert(NTW <= NW, "one finishing wave per tile");
-    constexpr bool XC = ZK_GF_XC && XR == 2 && !LN && !MRG;          // activation copied to LDS (see above)
+    constexpr bool XC = XR == 2 && !LN && !MRG;          // activation copied to LDS (see above)
     constexpr bool XS = LN || MRG || XC;                             // activation from LDS
     constexpr int XSTR = XC ? NW * KS * 32 + 8 : GF_XS;              // LDS image row stride (bf16)
     constexpr int XCN = XC ? KS * 32 * 2 / 512 : 1;                  // XC: 16-B loads per lane (2 rows)
@@ -785,9 +696,9 @@ __global__ __launch_bounds__(64 * NW, XR == 2 ? ZK_GF_OCC2 : 1) void k_gemv_f(co
     // keep the compiler from moving these loads behind the prefetch.
     constexpr int NJ = LN ? 4 : 1;                                   // 16-B chunks per lane per row
     uint4 xv[LN ? MR : 1][NJ] = {}, wv[NJ] = {}, bv[NJ] = {};
-    // ZK_GF_LNW (B = 1): only the waves that normalise a row (w < M) load the row and the LayerNorm
+    // B = 1: only the waves that normalise a row (w < M) load the row and the LayerNorm
     // weights; the others issue nothing before their weight prefetch (wave-uniform branch)
-    if constexpr (LN) if (!(ZK_GF_LNW && XR == 2 && MR == 1) || w < M) {
+    if constexpr (LN) if (!(XR == 2 && MR == 1) || w < M) {
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
             wv[j] = *reinterpret_cast<const uint4*>(lnw + lane * 8 + j * 512);
@@ -855,7 +766,7 @@ __global__ __launch_bounds__(64 * NW, XR == 2 ? ZK_GF_OCC2 : 1) void k_gemv_f(co
     uint4 wr[U][NTW], ar[U][KPL];
     auto issue = [&](int ls, int slot) {
 #pragma unroll
-        for (int tt = 0; tt < NTW; ++tt) wr[slot][tt] = ldg_w<true>(wp[tt] + ls * 512 * KPL);
+        for (int tt = 0; tt < NTW; ++tt) wr[slot][tt] = ldg_w(wp[tt] + ls * 512 * KPL);
         if constexpr (!XS) {
 #pragma unroll
             for (int q = 0; q < KPL; ++q) ar[slot][q] = *reinterpret_cast<const uint4*>(ap + (ls * KPL + q) * 32);
@@ -1144,25 +1055,7 @@ static bool ws_regime(int M, int K, int nsplit) {
     return M <= BM && K / nsplit / BK <= 32;
 }
 
-// k_gemm_ws column groups per compute wave (NG): 16 * 4 * NG columns per workgroup. The slab
-// epilogue needs N % 4 == 0 for its whole-row stores (the heads GEMM, N = 9234, keeps NG = 1).
-#ifndef ZK_WS_NG0
-#define ZK_WS_NG0 1                // split-K slab GEMMs (mode 0)
-#endif
-#ifndef ZK_WS_NG1
-#define ZK_WS_NG1 1                // SwiGLU fc1 (mode 1)
-#endif
-#ifndef ZK_WS_NGNB
-#define ZK_WS_NGNB 1               // activation fragment buffers at NG = 2 (2 exceeds 256 VGPRs at PF 3)
-#endif
-static int ws_ng(int N, int mode) {
-    if (mode == 1) return ZK_WS_NG1;
-    return N % 4 == 0 ? ZK_WS_NG0 : 1;
-}
-
-#ifndef ZK_GEMM_PF
-#define ZK_GEMM_PF 1               // 256 x 256-tile prefill GEMM (gemm_pf.hip) where it fills the chip
-#endif
+// 256 x 256-tile prefill GEMM (gemm_pf.hip) where it fills the chip
 bool zk_gemm_pf_applies(int M, int N, int K, int nsplit);
 int zk_gemm_pf(const void* A, long lda, const void* W, int M, int N, int K, int mode, float* C, void* Cb,
                const int32_t* skip, void* stream);
@@ -1170,8 +1063,8 @@ int zk_gemm_pf(const void* A, long lda, const void* W, int M, int N, int K, int 
 // k_gemm_ws compute waves per workgroup for this GEMM: 4 (64 columns), or for the slab GEMMs whose
 // 64-column grid fits the 256 CUs badly ZK_WS_NARROW (fewer than ZK_WS_NARROW_BELOW workgroups: more,
 // narrower ones) or ZK_WS_WIDE (more than 256: fewer, wider ones, so no CU runs two)
-static int ws_ncw(int M, int N, int nsplit, int mode, int ng) {
-    if (ZK_WS_NCW != 4 || mode != 0 || M <= 64 || ng != 1) return ZK_WS_NCW;
+static int ws_ncw(int M, int N, int nsplit, int mode) {
+    if (ZK_WS_NCW != 4 || mode != 0 || M <= 64) return ZK_WS_NCW;
     auto tiles = [&](int nw) { return (long)((N + 16 * nw - 1) / (16 * nw)) * nsplit; };
     if (ZK_WS_NARROW > 0 && tiles(4) < ZK_WS_NARROW_BELOW)
         for (int nw = ZK_WS_NARROW; nw <= 3; ++nw)          // the largest grid that still fits the CUs
@@ -1183,13 +1076,10 @@ static int ws_ncw(int M, int N, int nsplit, int mode, int ng) {
 ZkWarm zk_gemm_warm_desc(const void* W, int M, int N, int K, int nsplit, int mode, int chunks) {
     if (W == nullptr || M <= 16 || ZK_WS_NCW != 4 || !ws_regime(M, K, nsplit) || K % (nsplit * BK) != 0)
         return ZkWarm{nullptr, 0, 0, 0, 0};
-    const int ng = ws_ng(N, mode);
-    const int nw = ws_ncw(M, N, nsplit, mode, ng);
-    const int gx = (N + 16 * nw * ng - 1) / (16 * nw * ng);
-    const int excess = gx * nw * ng - (N + 15) / 16;            // grid tiles wholly past N (< nw * ng)
-    return ZkWarm{W, K, gx, nsplit,
-                  std::min(chunks, K / nsplit / BK) | (ng > 1 ? ng << 8 : 0) | (nw != 4 ? nw << 16 : 0) |
-                      (excess << 24)};
+    const int nw = ws_ncw(M, N, nsplit, mode);
+    const int gx = (N + 16 * nw - 1) / (16 * nw);
+    const int excess = gx * nw - (N + 15) / 16;                 // grid tiles wholly past N (< nw)
+    return ZkWarm{W, K, gx, nsplit, std::min(chunks, K / nsplit / BK) | (nw != 4 ? nw << 16 : 0) | (excess << 24)};
 }
 
 // Host mirror of warm_unit's tile bound for the descriptor zk_gemm_warm_desc builds: the number of
@@ -1262,20 +1152,18 @@ int zk_gemm_bf16_warm(const void* A, long lda, const void* W, int M, int N, int 
     }
     if (M <= BM && nchunks <= 32) {
         constexpr int NCW = ZK_WS_NCW;            // compute waves per workgroup
-        const int ng = M > 16 && NCW == 4 ? ws_ng(N, mode) : 1;
         // a slab GEMM whose 64-column tiles x splits leave a quarter of the CUs idle (the c5 Mamba
         // in_proj: N = 8512 unsplit, 133 tiles; the c3 out_proj, split 4: 128) runs narrower
         // workgroups of 2 or 3 compute waves (16 columns each), the most that still fit one
         // workgroup per CU (the Mamba in_proj at 2 waves would be 266 workgroups for 256 CUs:
         // c5 decode 4.34 -> 4.64 ms); the same per-column K order (bit-identical results).
-        const int ncw = M > 16 ? ws_ncw(M, N, nsplit, mode, ng) : NCW;
-        dim3 g((N + 16 * ncw * ng - 1) / (16 * ncw * ng), 1, nsplit);
+        const int ncw = M > 16 ? ws_ncw(M, N, nsplit, mode) : NCW;
+        dim3 g((N + 16 * ncw - 1) / (16 * ncw), 1, nsplit);
         const int MT = M <= 16 ? 1 : (M <= 32 ? 2 : (M <= 64 ? 4 : 8));
         const size_t lds = (size_t)WS_NB * MT * 16 * BK * 2 + (warm.W ? 1024 : 0);     // + warm-up sink
-#define ZK_WS_LAUNCH5(MODE_, NCH_, MT_, NG_, NCW_)                                                                 \
+#define ZK_WS_LAUNCH4(MODE_, NCH_, MT_, NCW_)                                                                      \
     do {                                                                                                          \
-        constexpr int NB_ = NG_ > 1 ? ZK_WS_NGNB : (NCW_ > 5 ? 1 : 2);                                            \
-        auto kern_ = &k_gemm_ws<MODE_, NCH_, (MODE_ ? WS_PF : WS_PF0), MT_, NCW_, NG_, NB_>;                       \
+        auto kern_ = &k_gemm_ws<MODE_, NCH_, (MODE_ ? WS_PF : WS_PF0), MT_, NCW_>;                                 \
         if (lds > 65536)                                                                                          \
             hipFuncSetAttribute(reinterpret_cast<const void*>(kern_), hipFuncAttributeMaxDynamicSharedMemorySize, \
                                 (int)lds);                                                                        \
@@ -1284,17 +1172,13 @@ int zk_gemm_bf16_warm(const void* A, long lda, const void* W, int M, int N, int 
                            skip_flag, (const bf16_t*)warm.W, warm.K, warm.gx, warm.gz, warm.chunks);              \
         handled = true;                                                                                           \
     } while (0)
-#define ZK_WS_LAUNCH4(MODE_, NCH_, MT_, NG_) ZK_WS_LAUNCH5(MODE_, NCH_, MT_, NG_, NCW)
 #define ZK_WS_LAUNCH3(MODE_, NCH_, MT_)                                                                            \
     do {                                                                                                          \
-        if ((MT_) == 8 && ng == 2) ZK_WS_LAUNCH4(MODE_, NCH_, MT_, 2);                                            \
-        else if ((MODE_) == 0 && (MT_) == 8 && ncw == 2 && NCW == 4)                                              \
-            ZK_WS_LAUNCH5(MODE_, NCH_, MT_, 1, 2);                                                                 \
-        else if ((MODE_) == 0 && (MT_) == 8 && ncw == 3 && NCW == 4)                                              \
-            ZK_WS_LAUNCH5(MODE_, NCH_, MT_, 1, 3);                                                                 \
+        if ((MODE_) == 0 && (MT_) == 8 && ncw == 2 && NCW == 4) ZK_WS_LAUNCH4(MODE_, NCH_, MT_, 2);               \
+        else if ((MODE_) == 0 && (MT_) == 8 && ncw == 3 && NCW == 4) ZK_WS_LAUNCH4(MODE_, NCH_, MT_, 3);          \
         else if ((MODE_) == 0 && (MT_) == 8 && ncw == ZK_WS_WIDE_W && ncw != NCW)                                   \
-            ZK_WS_LAUNCH5(MODE_, NCH_, MT_, 1, ZK_WS_WIDE_W);                                                      \
-        else ZK_WS_LAUNCH4(MODE_, NCH_, MT_, 1);                                                                  \
+            ZK_WS_LAUNCH4(MODE_, NCH_, MT_, ZK_WS_WIDE_W);                                                         \
+        else ZK_WS_LAUNCH4(MODE_, NCH_, MT_, NCW);                                                                \
     } while (0)
 #define ZK_WS_LAUNCH(MODE_, NCH_)                                                                                  \
     do {                                                                                                          \
@@ -1328,13 +1212,12 @@ int zk_gemm_bf16_warm(const void* A, long lda, const void* W, int M, int N, int 
             ZK_CHECK_LAUNCH("zk_gemm_bf16");
             return 0;
         }
-#undef ZK_WS_LAUNCH5
 #undef ZK_WS_LAUNCH4
 #undef ZK_WS_LAUNCH3
 #undef ZK_WS_LAUNCH
     }
     // large M (prefill) with at least one 256 x 256 tile per CU: gemm_pf.hip
-    if (ZK_GEMM_PF && zk_gemm_pf_applies(M, N, K, nsplit))
+    if (zk_gemm_pf_applies(M, N, K, nsplit))
         return zk_gemm_pf(A, lda, W, M, N, K, mode, Cpart, Cout, skip_flag, stream);
     // large M (prefill): two 16-column tiles per wave for the slab GEMMs (c3 prefill: in_proj
     // 1.01 vs 1.09 ms, fc2 1.98 vs 2.29 ms; the SwiGLU fc1 is faster with one: 4.87 vs 5.24 ms)
@@ -1344,7 +1227,7 @@ int zk_gemm_bf16_warm(const void* A, long lda, const void* W, int M, int N, int 
 #define ZK_GEMM_LAUNCH(MODE_, U_)                                                                         \
     do {                                                                                                  \
         if (ntw == 2)                                                                                     \
-            hipLaunchKernelGGL((k_gemm<MODE_, U_, false, 2>), grid, dim3(NT), 0, (hipStream_t)stream,     \
+            hipLaunchKernelGGL((k_gemm<MODE_, U_, 2>)       , grid, dim3(NT), 0, (hipStream_t)stream,     \
                                (const bf16_t*)A, lda, (const bf16_t*)W, M, N, K, K / nsplit, Cpart,       \
                                (bf16_t*)Cout, skip_flag);                                                 \
         else                                                                                              \
@@ -1393,9 +1276,6 @@ extern "C" int zk_gemv_fused(const void* A, long lda, const void* W, int M, int 
 #ifndef ZK_GF_PF
 #define ZK_GF_PF 8
 #endif
-#ifndef ZK_GF_PF2
-#define ZK_GF_PF2 ZK_GF_PF         // k-steps in flight of the B = 1 (XR = 2) instantiations
-#endif
 #ifndef ZK_GF_PFLN
 #define ZK_GF_PFLN 12              // k-steps in flight of the B = 1 LayerNorm-prologue one-tile GEMV (in_proj):
 #endif                             // c2 step 1.045-1.048 vs 1.051-1.053 ms at 8, 1.054-1.055 at 16 (r3_b1_gemv_pf_ab)
@@ -1403,7 +1283,7 @@ extern "C" int zk_gemv_fused(const void* A, long lda, const void* W, int M, int 
     do {                                                                                                      \
         constexpr int KS_ = (KSW_) / (NW_);                                                                   \
         constexpr int NL_ = HALF_ ? KS_ / 2 : KS_;                                                            \
-        constexpr int PB_ = (LN_ && NTW_ == 1 && !HALF_) ? ZK_GF_PFLN : ZK_GF_PF2;                            \
+        constexpr int PB_ = (LN_ && NTW_ == 1 && !HALF_) ? ZK_GF_PFLN : ZK_GF_PF;                           \
         if (M <= 2)                                                                               \
             hipLaunchKernelGGL((k_gemv_f<MODE_, LN_, NTW_, HALF_, NW_, KS_, (NL_ < PB_ ? NL_ : PB_),              \
                                           0, 2>),                                                             \

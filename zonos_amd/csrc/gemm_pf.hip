@@ -10,7 +10,7 @@
 // weights as the fragment-packed image itself ([N/16][K/32][64 lanes][8]: every 16 x 32 B
 // fragment is a lane-linear 1 KB block, so the copy needs no address math and the read no swizzle).
 // The next step's stage is issued after the barrier that retires the stage it overwrites, one
-// piece per 4 MFMAs over the step's first k-slice (ZK_PF_SPREAD), so the rest of the step covers its
+// piece per 4 MFMAs over the step's first k-slice (PF_SPREAD), so the rest of the step covers its
 // latency and the issues do not stall the MFMAs. Tiles are handed to the 8 XCDs in
 // contiguous runs and walked in 4 x 8 (row x column) blocks, so each XCD's L2 re-serves both
 // operands to the 32 workgroups it runs at once.
@@ -25,31 +25,15 @@
 namespace {
 
 constexpr int PF_BM = 256, PF_NT = 512;
-#ifndef ZK_PF_EPI
-#define ZK_PF_EPI 1                        // LDS-staged whole-row epilogues (0: direct register stores, A/B)
-#endif
-// diagnostic builds only (timing of the main loop's parts; results are wrong): NOWAIT skips the copy
-// waits (the barrier stays), NOMFMA the MFMAs (the LDS reads stay), NOLDS the LDS fragment reads
-#ifndef ZK_PF_DIAG_NOWAIT
-#define ZK_PF_DIAG_NOWAIT 0
-#endif
-#ifndef ZK_PF_DIAG_NOFILL          // (no LDS-DMA at all: MFMAs + LDS reads + barriers only)
-#define ZK_PF_DIAG_NOFILL 0
-#endif
-#ifndef ZK_PF_DIAG_NOEPI           // (no epilogue stores)
-#define ZK_PF_DIAG_NOEPI 0
-#endif
-#ifndef ZK_PF_DIAG_NOMFMA
-#define ZK_PF_DIAG_NOMFMA 0
-#endif
-// the refill of the next stage: piece j of a wave issued right after MFMA j * ZK_PF_SPREAD of the step
-// (0: all pieces at the top of the step). A burst of 8 LDS-DMA issues holds the wave's MFMAs back;
+// the refill of the next stage: piece j of a wave issued right after MFMA j * PF_SPREAD of the step
+// (not all pieces at the top of the step). A burst of 8 LDS-DMA issues holds the wave's MFMAs back;
 // one piece per 4 MFMAs (over the step's first k-slice) measured fastest: fc1 3.31-3.38 -> 3.18 ms,
 // qkv 0.77 -> 0.73, o 0.47-0.48 -> 0.45, fc2 1.50 -> 1.42 (1, 2 or 8 MFMAs per piece, 32-deep stages
 // and 256 x 384 tiles slower; profiles/r5_prefill_spread_ab.txt)
-#ifndef ZK_PF_SPREAD
-#define ZK_PF_SPREAD 4
-#endif
+constexpr int PF_SPREAD = 4;
+// diagnostic builds only (results are wrong): the LDS fragment reads replaced by register values, to time
+// the main loop without them (profiles/r5_prefill_diag.txt). Kept: without this arm the fragment-read
+// lambdas no longer capture the step counter and hipcc allocates the K loop's scalars differently.
 #ifndef ZK_PF_DIAG_NOLDS
 #define ZK_PF_DIAG_NOLDS 0
 #endif
@@ -300,7 +284,6 @@ __global__ __launch_bounds__(PF_NT, 1) void k_gemm_pf(const bf16_t* __restrict__
     }
     const uint32_t lds0 = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)smem + w * 1024);
     auto issue = [&](int kt, int st) {
-        if (ZK_PF_DIAG_NOFILL) return;
         const uint32_t sa = lds0 + st * ST, sb = sa + AST;
 #pragma unroll
         for (int i = 0; i < NA; ++i) pf_glds_s(abase + kt * BKS, aoff[i], sa + i * 8192);
@@ -310,16 +293,14 @@ __global__ __launch_bounds__(PF_NT, 1) void k_gemm_pf(const bf16_t* __restrict__
     constexpr int LPS = NA + NB;                         // LDS-DMA loads per wave and stage
     // one piece j of the stage: activation pieces first, then weight pieces
     auto issue_piece = [&](int kt, int st, int j) {
-        if (ZK_PF_DIAG_NOFILL) return;
         const uint32_t sa = lds0 + st * ST, sb = sa + AST;
         if (j < NA) pf_glds_s(abase + kt * BKS, aoff[j], sa + j * 8192);
         else pf_glds_s(W + (size_t)kt * KSS * 512, boff[j - NA], sb + (j - NA) * 8192);
     };
-    // ZK_PF_SPREAD = P > 0: the refill's pieces are issued between the step's MFMAs, piece j right after
-    // MFMA j * P of the step, instead of all at the top of the step (0)
+    // the refill's pieces are issued between the step's MFMAs, piece j right after MFMA j * SP of the step
     constexpr int QS = KSS * 8;                          // MFMA groups (ks, mt) per step
-    constexpr int SP = ZK_PF_SPREAD;
-    static_assert(SP == 0 || (LPS - 1) * SP < QS * NTN, "spread: every piece inside the step");
+    constexpr int SP = PF_SPREAD;
+    static_assert(SP > 0 && (LPS - 1) * SP < QS * NTN, "spread: every piece inside the step");
 
     f32x4 acc[8][NTN];
 #pragma unroll
@@ -333,17 +314,13 @@ __global__ __launch_bounds__(PF_NT, 1) void k_gemm_pf(const bf16_t* __restrict__
     for (int kt = 0; kt < nk; ++kt) {
         // step kt's copies: everything issued after them may stay in flight (with the spread refill every
         // step issues one stage, clamped past the end, so that is NSTG - 2 stages once the ring is full)
-        const int after = ZK_PF_SPREAD ? min(NSTG - 2, min(NSTG - 1, nk) - 1) : min(NSTG - 2, nk - 1 - kt);
-        if constexpr (ZK_PF_DIAG_NOWAIT) {
-        } else {
-            pf_wait_after<LPS, NSTG - 2>(after);
-        }
+        const int after = min(NSTG - 2, min(NSTG - 1, nk) - 1);
+        pf_wait_after<LPS, NSTG - 2>(after);
         // the barrier publishes every wave's copies of step kt and ends every read of the stage the
         // refill below overwrites (read in step kt - 1; this wave's reads retired here)
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
-        if (!ZK_PF_SPREAD && kt + NSTG - 1 < nk) issue(kt + NSTG - 1, (kt + NSTG - 1) % NSTG);
         const char* sa = smem + (kt % NSTG) * ST;
         const char* sb = sa + AST;
         auto rd_a = [&](int q) -> uint4 {
@@ -368,35 +345,20 @@ __global__ __launch_bounds__(PF_NT, 1) void k_gemm_pf(const bf16_t* __restrict__
             }
 #pragma unroll
             for (int nt = 0; nt < NTN; ++nt) {
-                if constexpr (ZK_PF_DIAG_NOMFMA) {
-                    acc[mt][nt][0] += __uint_as_float(a.x ^ bf[ks & 1][nt].y);
-                } else {
-                    acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_frag(a), as_frag(bf[ks & 1][nt]), acc[mt][nt],
-                                                                          0, 0, 0);
-                }
-                if constexpr (SP != 0) {
-                    // no branch around the pieces (one basic block per step, so the LDS reads can be
-                    // scheduled ahead of the MFMAs): past the last step the refill re-reads step nk - 1
-                    // into the stage nothing reads any more (the epilogue drains vmcnt first)
-                    const int f = q * NTN + nt;
-                    if (f % SP == 0 && f / SP < LPS)
-                        issue_piece(min(kt + NSTG - 1, nk - 1), (kt + NSTG - 1) % NSTG, f / SP);
-                }
+                acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_frag(a), as_frag(bf[ks & 1][nt]), acc[mt][nt],
+                                                                      0, 0, 0);
+                // no branch around the pieces (one basic block per step, so the LDS reads can be
+                // scheduled ahead of the MFMAs): past the last step the refill re-reads step nk - 1
+                // into the stage nothing reads any more (the epilogue drains vmcnt first)
+                const int f = q * NTN + nt;
+                if (f % SP == 0 && f / SP < LPS)
+                    issue_piece(min(kt + NSTG - 1, nk - 1), (kt + NSTG - 1) % NSTG, f / SP);
             }
             if (q + 1 < QS) a = rd_a(q + 1);
         }
     }
 
-    if constexpr (ZK_PF_DIAG_NOEPI) {          // (diagnostic: no stores; one lane keeps the sums live)
-        float t = 0.f;
-#pragma unroll
-        for (int mt = 0; mt < 8; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < NTN; ++nt) t += acc[mt][nt][0] + acc[mt][nt][3];
-        if (t == 1.2345f && C) C[0] = t;
-        return;
-    }
-    if constexpr (ZK_PF_EPI && (MODE == 1 || NTN == 4)) {
+    if constexpr (MODE == 1 || NTN == 4) {
         if (MODE == 1 || N % 4 == 0) {
             pf_epilogue_lds<MODE, NTN>(acc, smem, m0, n0, wr, wc, ln, lg, M, N, C, Cb);
             return;
@@ -414,28 +376,18 @@ bool zk_gemm_pf_applies(int M, int N, int K, int nsplit) {
     return tiles >= 256;                              // at least one tile per CU
 }
 
-// stage depth and ring length: 64-deep stages x 2 (default), or 32-deep x 4 (3 in flight; 128 KB either
-// way): 32 x 4 measured 2-4 % slower at the c3 prefill shapes (profiles/r4_prefill_gemm_bks_ab.txt), so the
-// kernel is not waiting on copy latency
-#ifndef ZK_PF_BKS
-#define ZK_PF_BKS 64
-#endif
-// 256 x 384 tiles for the SwiGLU (fc1) form when N >= 8192 (the partial last column tile wastes <= 1.6 %
-// of its MFMAs there); 0: 256 x 256 everywhere
-#ifndef ZK_PF_WIDE
-#define ZK_PF_WIDE 0
-#endif
-#ifndef ZK_PF_NSTG
-#define ZK_PF_NSTG (ZK_PF_BKS == 64 ? 2 : 4)
-#endif
-constexpr int PF_BKS = ZK_PF_BKS, PF_NSTG = ZK_PF_NSTG;
+// stage depth and ring length: 64-deep stages x 2. 32-deep x 4 (3 in flight; 128 KB either way)
+// measured 2-4 % slower at the c3 prefill shapes: profiles/r4_prefill_gemm_bks_ab.txt (so the kernel
+// is not waiting on copy latency). 256 x 384 tiles for the SwiGLU (fc1) form measured slower:
+// profiles/r5_prefill_spread_ab.txt
+constexpr int PF_BKS = 64, PF_NSTG = 2;
 constexpr int pf_max(int a, int b) { return a > b ? a : b; }
 template <int MODE, int NTN>
 constexpr int pf_lds() {
     return pf_max(PF_NSTG * (PF_BM + pf_bn<NTN>) * PF_BKS * 2,
-                  ZK_PF_EPI ? (MODE == 1 ? pf_epi_lds1<NTN> : pf_epi_lds0<NTN>) : 0);
+                  MODE == 1 ? pf_epi_lds1<NTN> : pf_epi_lds0<NTN>);
 }
-static_assert((!ZK_PF_WIDE || pf_lds<1, 6>() <= 163840) && pf_lds<0, 4>() <= 163840 && pf_lds<1, 4>() <= 163840, "LDS");
+static_assert(pf_lds<0, 4>() <= 163840 && pf_lds<1, 4>() <= 163840, "LDS");
 
 template <int MODE, int NTN>
 static int pf_launch(const void* A, long lda, const void* W, int M, int N, int K, float* C, void* Cb,
@@ -459,10 +411,6 @@ int zk_gemm_pf(const void* A, long lda, const void* W, int M, int N, int K, int 
     // overlapping the other's MFMAs -- measured 1-3 % slower: DESIGN.md §6 round 4)
     const hipStream_t st = (hipStream_t)stream;
     int rc;
-#if ZK_PF_WIDE
-    if (mode == 1 && N >= 8192) rc = pf_launch<1, 6>(A, lda, W, M, N, K, C, Cb, skip, st);
-    else
-#endif
     if (mode == 0) rc = pf_launch<0, 4>(A, lda, W, M, N, K, C, Cb, skip, st);
     else rc = pf_launch<1, 4>(A, lda, W, M, N, K, C, Cb, skip, st);
     if (rc) return rc;

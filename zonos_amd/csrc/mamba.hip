@@ -139,28 +139,18 @@ __global__ __launch_bounds__(MB_THREADS) void k_mamba_step(
 // heads' SSM state slices are in flight during the prologue, and the heads are then streamed
 // with the next head's state loads in flight while the current one is updated. The per-element
 // arithmetic and the y reduction are those of k_mamba_step (bit-identical outputs and states).
-#ifndef ZK_MB_HG
-#define ZK_MB_HG 1                   // heads per workgroup (1: 54.4 us, 2: 60.2, 4: 61.9, 8: 68.6 at c5; tools/mamba_ab.sh)
-#endif
-#ifndef ZK_MB_PD
-#define ZK_MB_PD 1                   // heads' state slices in flight
-#endif
-#ifndef ZK_MB_DEFER
-#define ZK_MB_DEFER 1                // k_mamba_step_g / k_gated_norm test the step word after their first loads
-#endif
-#ifndef ZK_MB_NT
-#define ZK_MB_NT 3                   // non-temporal SSM state loads (1) / stores (2): c5 decode 4.42 -> 4.34 ms (the stores; loads alone 4.47-4.49)
-#endif
+// k_mamba_step_g and k_gated_norm test the step word after their first loads.
+constexpr int MB_HG = 1;             // heads per workgroup (1: 54.4 us, 2: 60.2, 4: 61.9, 8: 68.6 at c5; no raw output
+                                     // kept; the first sweep, before ping-pong: profiles/r2_mamba_step_grouped_ab.txt)
+constexpr int MB_PD = 1;             // heads' state slices in flight
+// non-temporal SSM state loads and stores: c5 decode 4.42 -> 4.34 ms (the stores; loads alone
+// 4.47-4.49): profiles/r4_c5_mamba_nt_ab.txt
 typedef __attribute__((ext_vector_type(4))) unsigned int mb_u32x4;
 __device__ __forceinline__ uint4 mb_ld_state(const bf16_t* p) {
-    if constexpr (ZK_MB_NT & 1)
-        return __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const mb_u32x4*>(p)));
-    else return *reinterpret_cast<const uint4*>(p);
+    return __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const mb_u32x4*>(p)));
 }
 __device__ __forceinline__ void mb_st_state(bf16_t* p, uint4 v) {
-    if constexpr (ZK_MB_NT & 2)
-        __builtin_nontemporal_store(__builtin_bit_cast(mb_u32x4, v), reinterpret_cast<mb_u32x4*>(p));
-    else *reinterpret_cast<uint4*>(p) = v;
+    __builtin_nontemporal_store(__builtin_bit_cast(mb_u32x4, v), reinterpret_cast<mb_u32x4*>(p));
 }
 template <int HP, int DS, int HG, int GS>
 __global__ __launch_bounds__(MB_THREADS) void k_mamba_step_g(
@@ -178,8 +168,6 @@ __global__ __launch_bounds__(MB_THREADS) void k_mamba_step_g(
     constexpr int NIT = (NI + MB_THREADS - 1) / MB_THREADS;
     static_assert(TPP * HP == MB_THREADS && EPT * TPP == DS && EPT % 8 == 0, "tile");
     __shared__ float s_x[NX], s_z[NX], s_B[DS], s_C[DS], s_dt[HG];
-    if (!ZK_MB_DEFER)
-        if (skip && *skip) return;
     const int h0 = blockIdx.x * HG, r = blockIdx.y;
     const int conv_dim = di + 2 * DS;
     const int ncol = 2 * di + 2 * DS + nh;
@@ -220,7 +208,7 @@ __global__ __launch_bounds__(MB_THREADS) void k_mamba_step_g(
     // for v = 0..NV-1, row pv = (w*NV + v)*4 + L/16, channels 8*(L%16) .. +7 -- instead of 16 B of
     // every 64 B (thread-contiguous 64-B runs: each instruction touching 32 lines partially).
     constexpr bool COAL = DS == 128 && HP * DS / 8 == MB_THREADS * NV;
-    constexpr int PD = ZK_MB_PD < HG ? ZK_MB_PD : HG;
+    constexpr int PD = MB_PD < HG ? MB_PD : HG;
     const int lw = t >> 6, ll = t & 63;
     uint4 st[PD][NV];
     auto st_off = [&](int v) -> size_t {        // element offset of piece v in the (row, head) state
@@ -234,23 +222,21 @@ __global__ __launch_bounds__(MB_THREADS) void k_mamba_step_g(
     };
 #pragma unroll
     for (int hh = 0; hh < PD; ++hh) load_state(hh, hh);
-    if constexpr (ZK_MB_DEFER) {
-        // the step word once the prologue and the first state slices are in flight (every load above
-        // is in bounds; nothing is written before this test)
-        if (ld_word_here(skip)) {
+    // the step word once the prologue and the first state slices are in flight (every load above
+    // is in bounds; nothing is written before this test)
+    if (ld_word_here(skip)) {
 #pragma unroll
-            for (int k = 0; k < NIT; ++k) {
+        for (int k = 0; k < NIT; ++k) {
 #pragma unroll
-                for (int g = 0; g < GS; ++g) asm volatile("" ::"v"(sv[k][g]));
-                asm volatile("" ::"v"(cst[k].x), "v"(cst[k].y), "v"(cb[k]));
-                keep_live(cw[k]);
-            }
-#pragma unroll
-            for (int hh = 0; hh < PD; ++hh)
-#pragma unroll
-                for (int v = 0; v < NV; ++v) keep_live(st[hh][v]);
-            return;
+            for (int g = 0; g < GS; ++g) asm volatile("" ::"v"(sv[k][g]));
+            asm volatile("" ::"v"(cst[k].x), "v"(cst[k].y), "v"(cb[k]));
+            keep_live(cw[k]);
         }
+#pragma unroll
+        for (int hh = 0; hh < PD; ++hh)
+#pragma unroll
+            for (int v = 0; v < NV; ++v) keep_live(st[hh][v]);
+        return;
     }
 
     // ---- prologue arithmetic (the per-item arithmetic of k_mamba_step)
@@ -447,7 +433,7 @@ __global__ __launch_bounds__(MB_THREADS) void k_gated_norm(const float* __restri
                                                            const float* __restrict__ w, float eps,
                                                            bf16_t* __restrict__ out, const int32_t* __restrict__ skip) {
     __shared__ float red[MB_THREADS / 64];
-    if (!ZK_MB_DEFER || di > GN_MAXJ * MB_THREADS)
+    if (di > GN_MAXJ * MB_THREADS)
         if (skip && *skip) return;
     const int row = blockIdx.x;
     const float* gr = g + (size_t)row * di;
@@ -461,12 +447,10 @@ __global__ __launch_bounds__(MB_THREADS) void k_gated_norm(const float* __restri
             gv[k] = j < di ? gr[j] : 0.f;
             wv[k] = j < di ? w[j] : 0.f;
         }
-        if constexpr (ZK_MB_DEFER) {
-            if (ld_word_here(skip)) {        // the step word after the row's loads (in bounds)
+        if (ld_word_here(skip)) {        // the step word after the row's loads (in bounds)
 #pragma unroll
-                for (int k = 0; k < GN_MAXJ; ++k) asm volatile("" ::"v"(gv[k]), "v"(wv[k]));
-                return;
-            }
+            for (int k = 0; k < GN_MAXJ; ++k) asm volatile("" ::"v"(gv[k]), "v"(wv[k]));
+            return;
         }
         float s = 0.f;
 #pragma unroll
@@ -495,7 +479,7 @@ __global__ __launch_bounds__(MB_THREADS) void k_gated_norm(const float* __restri
 
 namespace {
 
-// grouped = true: ZK_MB_HG heads per workgroup (default 1, the fastest measured; B/C conv once per
+// grouped = true: MB_HG heads per workgroup (default 1, the fastest measured; B/C conv once per
 // group), in_proj splits 1 / 2 / 4. grouped = false: one workgroup per (head, row), any split.
 int mamba_step(bool grouped, const float* part, int gemm_nsplit, int R, int d_inner, int nheads, int headdim,
                int d_state, const float* conv_w, const float* conv_b, void* conv_state_a, void* conv_state_b,
@@ -505,20 +489,20 @@ int mamba_step(bool grouped, const float* part, int gemm_nsplit, int R, int d_in
     ZK_REQUIRE(gemm_nsplit >= 1 && gemm_nsplit <= MB_MAXGS, "zk_mamba_step: gemm_nsplit=%d", gemm_nsplit);
     ZK_REQUIRE(nheads * headdim == d_inner, "zk_mamba_step: nheads*headdim != d_inner");
     bool handled = false;
-    if (grouped && nheads % ZK_MB_HG == 0 && (gemm_nsplit == 1 || gemm_nsplit == 2 || gemm_nsplit == 4)) {
+    if (grouped && nheads % MB_HG == 0 && (gemm_nsplit == 1 || gemm_nsplit == 2 || gemm_nsplit == 4)) {
 #define ZK_MB_STEPG(HP_, DS_)                                                                                       \
     do {                                                                                                           \
-        const dim3 g_(nheads / ZK_MB_HG, R);                                                                              \
+        const dim3 g_(nheads / MB_HG, R);                                                                                 \
         if (gemm_nsplit == 1)                                                                                      \
-            hipLaunchKernelGGL((k_mamba_step_g<HP_, DS_, ZK_MB_HG, 1>), g_, dim3(MB_THREADS), 0, (hipStream_t)stream,     \
+            hipLaunchKernelGGL((k_mamba_step_g<HP_, DS_, MB_HG, 1>), g_, dim3(MB_THREADS), 0, (hipStream_t)stream,     \
                                part, R, d_inner, nheads, conv_w, conv_b, (const bf16_t*)conv_state_a,             \
                                (bf16_t*)conv_state_b, pos_dev, (bf16_t*)ssm_state, (bf16_t*)ssm_state_b, A, dt_bias, D, yz, skip);      \
         else if (gemm_nsplit == 2)                                                                                 \
-            hipLaunchKernelGGL((k_mamba_step_g<HP_, DS_, ZK_MB_HG, 2>), g_, dim3(MB_THREADS), 0, (hipStream_t)stream,     \
+            hipLaunchKernelGGL((k_mamba_step_g<HP_, DS_, MB_HG, 2>), g_, dim3(MB_THREADS), 0, (hipStream_t)stream,     \
                                part, R, d_inner, nheads, conv_w, conv_b, (const bf16_t*)conv_state_a,             \
                                (bf16_t*)conv_state_b, pos_dev, (bf16_t*)ssm_state, (bf16_t*)ssm_state_b, A, dt_bias, D, yz, skip);      \
         else                                                                                                       \
-            hipLaunchKernelGGL((k_mamba_step_g<HP_, DS_, ZK_MB_HG, 4>), g_, dim3(MB_THREADS), 0, (hipStream_t)stream,     \
+            hipLaunchKernelGGL((k_mamba_step_g<HP_, DS_, MB_HG, 4>), g_, dim3(MB_THREADS), 0, (hipStream_t)stream,     \
                                part, R, d_inner, nheads, conv_w, conv_b, (const bf16_t*)conv_state_a,             \
                                (bf16_t*)conv_state_b, pos_dev, (bf16_t*)ssm_state, (bf16_t*)ssm_state_b, A, dt_bias, D, yz, skip);      \
     } while (0)
