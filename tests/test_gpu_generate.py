@@ -191,15 +191,26 @@ def test_multi_step_graph_equals_eager(poll, gsteps, monkeypatch):
         assert len(a) == len(b) and all(torch.equal(x, y) for x, y in zip(a, b)), case
 
 
-def test_fused_qkv_attention_equals_separate_kernels():
-    """zk_attn_decode_qkv (in_proj epilogue inside the attention launch) computes the same
-    numbers as zk_qkv_rope + zk_attn_decode: identical codes, bit for bit."""
+def test_fused_qkv_attention_equals_separate_kernels(monkeypatch):
+    """zk_attn_decode_qkv_sc (in_proj epilogue inside the attention launch) computes the same
+    numbers as zk_qkv_rope + zk_attn_decode: identical codes, bit for bit. Only the Python
+    sequence (c_step off) reads fuse_qkv, so the unfused run goes through it; its codes must be
+    those of the default C-path run and of the fused Python run."""
+    from zonos_amd.engine import HipDecoder
     c = load_gen_case("sampled_cli")
     eng = _engine(c["W"])
-    a = eng.generate(c["cond"].cuda(), c["prefix"].cuda(), c["max_new"], 2.0, c["B"], c["sp"], seed=9)
+
+    def run():
+        eng._ws = None
+        return eng.generate(c["cond"].cuda(), c["prefix"].cuda(), c["max_new"], 2.0, c["B"], c["sp"], seed=9)
+
+    c_path = run()
+    monkeypatch.setattr(HipDecoder, "c_step", False)
+    fused = run()
     eng.fuse_qkv = False
-    b = eng.generate(c["cond"].cuda(), c["prefix"].cuda(), c["max_new"], 2.0, c["B"], c["sp"], seed=9)
-    assert all(torch.equal(x, y) for x, y in zip(a, b))
+    unfused = run()
+    for other in (c_path, fused):
+        assert len(other) == len(unfused) and all(torch.equal(x, y) for x, y in zip(other, unfused))
 
 
 def test_teacher_forced_logits():

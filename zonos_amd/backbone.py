@@ -32,7 +32,7 @@ import torch.nn as nn
 from . import _lib
 from ._lib import call, ptr
 from .config import BackboneConfig, InferenceParams
-from .engine import ATTN_CHUNK, EngineConfig, HipBackbone, _split_for, attn_splits_for
+from .engine import ATTN_CHUNK, EngineConfig, HipBackbone, activation_buffers, attn_splits_for
 from .hybrid import HybridBackbone, HybridEngineConfig
 
 
@@ -106,27 +106,14 @@ class HipZonosBackbone(nn.Module):
         return {i: (kv[i], None) for i in range(c.n_layer)}
 
     def _workspace(self, R: int, S: int, smax: int) -> dict:
+        """Buffers of one forward over R rows x S positions (either backbone; S > 1 runs unsplit)."""
         key = (R, S, smax)
-        if self._ws is not None and self._ws["key"] == key:
-            return self._ws
-        c = self.ecfg
-        dev = self.norm_f.weight.device
-        D, H, Hk, hd, Fd = c.d_model, c.n_heads, c.n_kv, c.head_dim, c.d_ff
-        Nqkv = (H + 2 * Hk) * hd
-        M = R * S
-        f32, bf = torch.float32, torch.bfloat16
-        splits = dict(qkv=_split_for(Nqkv, D, M), o=_split_for(D, H * hd, M, target_blocks=128),
-                      fc2=_split_for(D, Fd, M))
-        if S > 1:
-            splits = dict(qkv=1, o=1, fc2=1)
-        attn_splits = attn_splits_for(R, Hk, smax)
-        part_n = max(M * Nqkv * splits["qkv"], M * D * max(splits["o"], splits["fc2"]))
-        self._ws = dict(key=key, R=R, smax=smax, splits=splits, attn_splits=attn_splits,
-                        x=torch.empty(M, D, dtype=bf, device=dev), xn=torch.empty(M, D, dtype=bf, device=dev),
-                        q=torch.empty(M, H * hd, dtype=bf, device=dev), y=torch.empty(M, H * hd, dtype=bf, device=dev),
-                        h=torch.empty(M, Fd, dtype=bf, device=dev), part=torch.empty(part_n, dtype=f32, device=dev),
-                        attn_work=torch.empty(max(1, R * Hk * attn_splits * (8 + 4 * hd)), dtype=f32, device=dev),
-                        scal=torch.zeros(16, dtype=torch.int32, device=dev))
+        if self._ws is None or self._ws["key"] != key:
+            splits = self._engine().splits(R)
+            attn_splits = attn_splits_for(R, self.ecfg.n_kv, smax)
+            self._ws = dict(key=key, R=R, smax=smax, splits=splits, attn_splits=attn_splits,
+                            **activation_buffers(self.ecfg, self.norm_f.weight.device, R * S, R, smax, splits,
+                                                 attn_splits))
         return self._ws
 
     def forward(self, hidden_states: torch.Tensor, inference_params: InferenceParams) -> torch.Tensor:
@@ -277,40 +264,6 @@ class HipHybridBackbone(HipZonosBackbone):
                 ssm = torch.zeros(2, batch_size, c.nheads_ssm, c.headdim, c.d_state, dtype=dtype, device=dev)
                 cache[i] = (conv, ssm)
         return cache
-
-    def _workspace(self, R: int, S: int, smax: int) -> dict:
-        if not self.hybrid:
-            return super()._workspace(R, S, smax)
-        key = (R, S, smax)
-        if self._ws is not None and self._ws["key"] == key:
-            return self._ws
-        c = self.ecfg
-        dev = self.norm_f.weight.device
-        D, H, Hk, hd, Fd = c.d_model, c.n_heads, c.n_kv, c.head_dim, c.d_ff
-        di, nin = c.d_inner, c.d_in_proj
-        Nqkv = (H + 2 * Hk) * hd
-        M = R * S
-        f32, bf = torch.float32, torch.bfloat16
-        if S > 1:
-            splits = dict(qkv=1, o=1, fc2=1, inp=1, out=1)
-        else:      # the decode engine's split rule (zonos_amd/hybrid.py HybridDecoder._alloc)
-            splits = dict(qkv=_split_for(Nqkv, D, R), o=_split_for(D, H * hd, R, target_blocks=128),
-                          fc2=_split_for(D, max(Fd, 64), R), inp=1, out=_split_for(D, di, R))
-        attn_splits = attn_splits_for(R, Hk, smax)
-        if c.d_mlp and not Fd and S == 1:
-            splits["fc2"] = _split_for(D, c.d_mlp, R)
-        part_n = max(M * Nqkv * splits["qkv"], M * D * max(splits["o"], splits["fc2"], splits["out"]), M * nin)
-        self._ws = dict(key=key, R=R, smax=smax, splits=splits, attn_splits=attn_splits,
-                        x=torch.empty(M, D, dtype=bf, device=dev), xn=torch.empty(M, D, dtype=bf, device=dev),
-                        xf=torch.empty(M, D, dtype=f32, device=dev) if c.residual_in_fp32 else None,
-                        q=torch.empty(M, H * hd, dtype=bf, device=dev), y=torch.empty(M, H * hd, dtype=bf, device=dev),
-                        h=torch.empty(M, max(Fd, c.d_mlp, 1), dtype=bf, device=dev),
-                        part=torch.empty(part_n, dtype=f32, device=dev),
-                        yz=torch.empty(M, di, dtype=f32, device=dev), ym=torch.empty(M, di, dtype=bf, device=dev),
-                        xc=torch.empty(M, c.conv_dim, dtype=bf, device=dev),
-                        attn_work=torch.empty(max(1, R * Hk * attn_splits * (8 + 4 * hd)), dtype=f32, device=dev),
-                        scal=torch.zeros(16, dtype=torch.int32, device=dev))
-        return self._ws
 
     def forward(self, hidden_states: torch.Tensor, inference_params: InferenceParams) -> torch.Tensor:
         if not self.hybrid:

@@ -118,8 +118,9 @@ extern "C" int zk_event_destroy(void* ev) {
 }
 
 // ------------------------------------------------------------------ one decode step
-// The launch sequence of zonos_amd.engine.HipDecoder._decode_step (see zonos_hip.h). Each
-// entry below checks its own arguments; the first failing one aborts the step with its message.
+// The launch sequences of zonos_amd.engine.HipDecoder and zonos_amd.hybrid.HybridDecoder (see
+// zonos_hip.h). Each entry below checks its own arguments; the first failing one aborts the step
+// with its message.
 #define ZK_STEP(call)                  \
     do {                               \
         if ((call) != 0) return -1;    \
@@ -131,8 +132,109 @@ static ZkWarm warm_desc(const void* W, int M, int N, int K, int nsplit, int mode
     return zk_gemm_warm_desc(W, M, N, K, nsplit, mode, 2);
 }
 
+namespace {
+const ZkWarm kNoWarm{nullptr, 0, 0, 0, 0};   // zk_resid_ln / zk_gemm_bf16 are their _warm forms with this
+
+// ---- what the transformer and the hybrid entries share: Desc is zk_step_desc or zk_hybrid_desc,
+// `who` the entry's name in its error messages
+
+// Prefill prologue: the argument checks, the prefix conditioning and the codebook embeddings into
+// x rows [2B][S = Lc + P + 1][D]. desc_ok: the entry's own descriptor check (false for d == nullptr).
+template <class Desc>
+int prefill_prologue(const char* who, bool desc_ok, const Desc* d, const void* cond, int Lc, int P, const void* q,
+                     void* stream) {
+    if (!desc_ok || cond == nullptr || q == nullptr || Lc < 0 || P < 0) {
+        zk_set_error("%s: bad arguments", who);
+        return -1;
+    }
+    // The last decode step attends over Lc + Ld keys (S = Lc + P + 1 after the prefill, plus
+    // Ld - (P + 1) steps, model.py:335-345). The decode attention clamps its context to smax so a
+    // no-op launch after the last step stays in bounds; a real step must never need that clamp.
+    if (Lc + d->st.Ld > d->smax) {
+        zk_set_error("%s: KV cache of %d keys is shorter than Lc + Ld = %d", who, d->smax, Lc + d->st.Ld);
+        return -1;
+    }
+    const int K = d->st.K, S = Lc + P + 1;
+    const size_t row = (size_t)d->d_model * 2;
+    // prefix conditioning into the first Lc positions of every row (model.py:184-186)
+    if (Lc > 0) {
+        hipError_t e = hipMemcpy2DAsync(d->x, S * row, cond, Lc * row, Lc * row, 2 * d->B, hipMemcpyDeviceToDevice,
+                                        (hipStream_t)stream);
+        if (e != hipSuccess) {
+            zk_set_error("%s: conditioning copy: %s", who, hipGetErrorString(e));
+            return -1;
+        }
+    }
+    return zk_embed_codes(d->st.delayed, d->B, P + 1, K, (long)d->st.Ld * K, d->st.Ld, nullptr, 0, d->emb, d->st.V,
+                          d->d_model, 2, d->x, S, Lc, nullptr, nullptr, d->eps, nullptr, nullptr, stream);
+}
+
+// Prefill epilogue: the heads on the last position of every row (rows r*S + S-1 via lda = S*D), the
+// first sample and the first frame write
+template <class Desc>
+int prefill_epilogue(const Desc* d, int S, int P, void* stream) {
+    const int R = 2 * d->B, D = d->d_model;
+    ZK_STEP(zk_gemm_bf16(static_cast<const char*>(d->xn) + (size_t)(S - 1) * D * 2, (long)S * D, d->heads, R,
+                         d->st.K * d->st.V, D, d->split_heads, 0, d->part, nullptr, nullptr, stream));
+    ZK_STEP(zk_sample_heads(d->part, d->split_heads, &d->st, &d->sp, 1, 0, d->dbg, stream));
+    return zk_eos_step(&d->st, 1, P + 1, stream);
+}
+
+// Decode tail: both sampler draws over the nsp logit slabs in part, then the EOS protocol
+template <class Desc>
+int decode_tail(const Desc* d, int nsp, void* stream) {
+    ZK_STEP(zk_sample_heads(d->part, nsp, &d->st, &d->sp, 0, 0, d->dbg, stream));
+    ZK_STEP(zk_sample_heads(d->part, nsp, &d->st, &d->sp, 0, 1, nullptr, stream));
+    return zk_eos_step(&d->st, 0, 0, stream);
+}
+
+// The seven-launch split-K block sequence of HipBackbone._layers over M = R*S rows, xn -> xn.
+// Prefill (S positions per row): splits of 1, no skip / position words, zk_qkv_rope +
+// zk_attn_prefill as the attention, no L2 warm-up.
+int transformer_layers(const zk_step_desc* d, int R, int S, bool prefill, void* q, void* stream) {
+    const int M = R * S;
+    const int D = d->d_model, H = d->n_heads, Hk = d->n_kv, hd = d->head_dim, Fd = d->d_ff;
+    const int Nqkv = (H + 2 * Hk) * hd;
+    const int32_t* skip = prefill ? nullptr : d->st.scal + 3;
+    const int32_t* pos = prefill ? nullptr : d->st.scal + 1;
+    const int sq = prefill ? 1 : d->split_qkv, so = prefill ? 1 : d->split_o, sf = prefill ? 1 : d->split_fc2;
+    // each k_resid_ln and the fc1 GEMM warm the next GEMM's first weight chunks into L2 (warm.h)
+    auto warm = [&](const void* W, int N, int K, int nsplit, int mode = 0) {
+        return prefill ? kNoWarm : warm_desc(W, M, N, K, nsplit, mode);
+    };
+    for (int i = 0; i < d->n_layer; ++i) {
+        const zk_step_layer& L = d->layers[i];
+        ZK_STEP(zk_gemm_bf16(d->xn, D, L.wqkv, M, Nqkv, D, sq, 0, d->part, nullptr, skip, stream));
+        if (prefill) {
+            ZK_STEP(zk_qkv_rope(d->part, 1, R, S, H, Hk, hd, d->freqs, 0, nullptr, q, L.k_cache, L.vt_cache, d->smax,
+                                nullptr, d->rope_neox, nullptr, stream));
+            ZK_STEP(zk_attn_prefill(q, L.k_cache, L.vt_cache, R, S, H, Hk, hd, d->smax, d->y, stream));
+        } else {
+            ZK_STEP(zk_attn_decode_qkv_sc(d->part, sq, d->freqs, L.k_cache, L.vt_cache, R, H, Hk, hd, d->smax, 1, pos,
+                                          d->attn_work, d->attn_splits, d->attn_cnt, d->y, d->rope_neox, skip,
+                                          stream));
+        }
+        ZK_STEP(zk_gemm_bf16(d->y, H * hd, L.wo, M, D, H * hd, so, 0, d->part, nullptr, skip, stream));
+        ZK_STEP(zk_resid_ln_warm(d->part, so, d->x, L.ln2_w, L.ln2_b, d->eps, M, D, d->x, d->xn, 0, skip,
+                                 warm(L.fc1, 2 * Fd, D, 1, 1), stream));
+        ZK_STEP(zk_gemm_bf16_warm(d->xn, D, L.fc1, M, 2 * Fd, D, 1, 1, nullptr, d->h, skip, warm(L.fc2, D, Fd, sf),
+                                  stream));
+        ZK_STEP(zk_gemm_bf16(d->h, Fd, L.fc2, M, D, Fd, sf, 0, d->part, nullptr, skip, stream));
+        const bool last = i + 1 == d->n_layer;
+        const ZkWarm next = last ? warm(d->heads, d->st.K * d->st.V, D, d->split_heads)
+                                 : warm(d->layers[i + 1].wqkv, Nqkv, D, sq);
+        ZK_STEP(zk_resid_ln_warm(d->part, sf, d->x, last ? d->lnf_w : d->layers[i + 1].ln1_w,
+                                 last ? d->lnf_b : d->layers[i + 1].ln1_b, d->eps, M, D, d->x, d->xn, 0, skip, next,
+                                 stream));
+    }
+    return 0;
+}
+
+bool step_ok(const zk_step_desc* d) { return d != nullptr && d->layers != nullptr && d->n_layer > 0 && d->B > 0; }
+}  // namespace
+
 extern "C" int zk_decode_step(const zk_step_desc* d, void* stream) {
-    if (d == nullptr || d->layers == nullptr || d->n_layer <= 0 || d->B <= 0) {
+    if (!step_ok(d)) {
         zk_set_error("zk_decode_step: bad descriptor");
         return -1;
     }
@@ -148,9 +250,15 @@ extern "C" int zk_decode_step(const zk_step_desc* d, void* stream) {
     ZK_STEP(zk_embed_codes(d->st.delayed, B, 1, K, (long)d->st.Ld * K, d->st.Ld, scal, -1, d->emb, V, D, 2, d->x, 1,
                            0, d->small ? nullptr : L0.ln1_w, d->small ? nullptr : L0.ln1_b, d->eps,
                            d->small ? nullptr : d->xn, skip, stream));
+    if (!d->small) {
+        ZK_STEP(transformer_layers(d, R, 1, false, nullptr, stream));
+        ZK_STEP(zk_gemm_bf16(d->xn, D, d->heads, R, K * V, D, d->split_heads, 0, d->part, nullptr, skip, stream));
+        return decode_tail(d, d->split_heads, stream);
+    }
+    // B <= 8: five launches per block, the attention (through out_proj) in one of three forms
     for (int i = 0; i < d->n_layer; ++i) {
         const zk_step_layer& L = d->layers[i];
-        if (d->small && d->attn_merge > 0 && !d->rope_neox) {
+        if (d->attn_merge > 0 && !d->rope_neox) {
             // B = 1: RoPE + KV write in the in_proj epilogue, a prologue-free attention over 32-key
             // slices, its partials merged by the out_proj GEMV
             ZK_STEP(zk_gemv_qkv_rope(d->x, L.wqkv, R, H, Hk, hd, L.ln1_w, L.ln1_b, d->eps, d->y, L.k_cache,
@@ -158,11 +266,7 @@ extern "C" int zk_decode_step(const zk_step_desc* d, void* stream) {
             ZK_STEP(zk_attn_decode_q_part(d->y, L.k_cache, L.vt_cache, R, H, Hk, hd, d->smax, 1, pos, d->attn_work,
                                           d->attn_merge, skip, stream));
             ZK_STEP(zk_gemv_attn_out(d->attn_work, d->attn_merge, Hk, L.wo, R, D, H * hd, d->x, skip, stream));
-            ZK_STEP(zk_gemv_fused(d->x, D, L.fc1, R, 2 * Fd, D, 1, L.ln2_w, L.ln2_b, d->eps, nullptr, d->h, skip,
-                                  stream));
-            ZK_STEP(zk_gemv_fused(d->h, Fd, L.fc2, R, D, Fd, 2, nullptr, nullptr, d->eps, nullptr, d->x, skip,
-                                  stream));
-        } else if (d->small) {
+        } else {
             ZK_STEP(zk_gemv_fused(d->x, D, L.wqkv, R, Nqkv, D, 0, L.ln1_w, L.ln1_b, d->eps, d->part, nullptr, skip,
                                   stream));
             if (d->attn_merge > 0) {
@@ -176,92 +280,22 @@ extern "C" int zk_decode_step(const zk_step_desc* d, void* stream) {
                 ZK_STEP(zk_gemv_fused(d->y, H * hd, L.wo, R, D, H * hd, 2, nullptr, nullptr, d->eps, nullptr, d->x,
                                       skip, stream));
             }
-            ZK_STEP(zk_gemv_fused(d->x, D, L.fc1, R, 2 * Fd, D, 1, L.ln2_w, L.ln2_b, d->eps, nullptr, d->h, skip,
-                                  stream));
-            ZK_STEP(zk_gemv_fused(d->h, Fd, L.fc2, R, D, Fd, 2, nullptr, nullptr, d->eps, nullptr, d->x, skip,
-                                  stream));
-        } else {
-            ZK_STEP(zk_gemm_bf16(d->xn, D, L.wqkv, R, Nqkv, D, d->split_qkv, 0, d->part, nullptr, skip, stream));
-            ZK_STEP(zk_attn_decode_qkv_sc(d->part, d->split_qkv, d->freqs, L.k_cache, L.vt_cache, R, H, Hk, hd,
-                                          d->smax, 1, pos, d->attn_work, d->attn_splits, d->attn_cnt, d->y,
-                                          d->rope_neox, skip, stream));
-            ZK_STEP(zk_gemm_bf16(d->y, H * hd, L.wo, R, D, H * hd, d->split_o, 0, d->part, nullptr, skip, stream));
-            // each k_resid_ln and the fc1 GEMM warm the next GEMM's first weight chunks into L2 (warm.h)
-            ZK_STEP(zk_resid_ln_warm(d->part, d->split_o, d->x, L.ln2_w, L.ln2_b, d->eps, R, D, d->x, d->xn, 0, skip,
-                                     warm_desc(L.fc1, R, 2 * Fd, D, 1, 1), stream));
-            ZK_STEP(zk_gemm_bf16_warm(d->xn, D, L.fc1, R, 2 * Fd, D, 1, 1, nullptr, d->h, skip,
-                                      warm_desc(L.fc2, R, D, Fd, d->split_fc2), stream));
-            ZK_STEP(zk_gemm_bf16(d->h, Fd, L.fc2, R, D, Fd, d->split_fc2, 0, d->part, nullptr, skip, stream));
-            const bool last = i + 1 == d->n_layer;
-            const ZkWarm next = last ? warm_desc(d->heads, R, K * V, D, d->split_heads)
-                                     : warm_desc(d->layers[i + 1].wqkv, R, Nqkv, D, d->split_qkv);
-            ZK_STEP(zk_resid_ln_warm(d->part, d->split_fc2, d->x, last ? d->lnf_w : d->layers[i + 1].ln1_w,
-                                     last ? d->lnf_b : d->layers[i + 1].ln1_b, d->eps, R, D, d->x, d->xn, 0, skip,
-                                     next, stream));
         }
+        ZK_STEP(zk_gemv_fused(d->x, D, L.fc1, R, 2 * Fd, D, 1, L.ln2_w, L.ln2_b, d->eps, nullptr, d->h, skip, stream));
+        ZK_STEP(zk_gemv_fused(d->h, Fd, L.fc2, R, D, Fd, 2, nullptr, nullptr, d->eps, nullptr, d->x, skip, stream));
     }
-    // 9 heads (model.py:104-111): small path with norm_f as the GEMV prologue, one slab
-    if (d->small)
-        ZK_STEP(zk_gemv_fused(d->x, D, d->heads, R, K * V, D, 0, d->lnf_w, d->lnf_b, d->eps, d->part, nullptr, skip,
-                              stream));
-    else
-        ZK_STEP(zk_gemm_bf16(d->xn, D, d->heads, R, K * V, D, d->split_heads, 0, d->part, nullptr, skip, stream));
-    const int nsp = d->small ? 1 : d->split_heads;
-    ZK_STEP(zk_sample_heads(d->part, nsp, &d->st, &d->sp, 0, 0, d->dbg, stream));
-    ZK_STEP(zk_sample_heads(d->part, nsp, &d->st, &d->sp, 0, 1, nullptr, stream));
-    ZK_STEP(zk_eos_step(&d->st, 0, 0, stream));
-    return 0;
+    // 9 heads (model.py:104-111) with norm_f as the GEMV prologue, one slab
+    ZK_STEP(zk_gemv_fused(d->x, D, d->heads, R, K * V, D, 0, d->lnf_w, d->lnf_b, d->eps, d->part, nullptr, skip,
+                          stream));
+    return decode_tail(d, 1, stream);
 }
 
 extern "C" int zk_prefill(const zk_step_desc* d, const void* cond, int Lc, int P, void* q, void* stream) {
-    if (d == nullptr || d->layers == nullptr || d->n_layer <= 0 || d->B <= 0 || cond == nullptr || q == nullptr ||
-        Lc < 0 || P < 0) {
-        zk_set_error("zk_prefill: bad arguments");
-        return -1;
-    }
-    // The last decode step attends over Lc + Ld keys (S = Lc + P + 1 after the prefill, plus
-    // Ld - (P + 1) steps, model.py:335-345). The decode attention clamps its context to smax so a
-    // no-op launch after the last step stays in bounds; a real step must never need that clamp.
-    if (Lc + d->st.Ld > d->smax) {
-        zk_set_error("zk_prefill: KV cache of %d keys is shorter than Lc + Ld = %d", d->smax, Lc + d->st.Ld);
-        return -1;
-    }
-    const int K = d->st.K, V = d->st.V, B = d->B, R = 2 * B, S = Lc + P + 1, M = R * S;
-    const int D = d->d_model, H = d->n_heads, Hk = d->n_kv, hd = d->head_dim, Fd = d->d_ff;
-    const int Nqkv = (H + 2 * Hk) * hd;
-    const size_t row = (size_t)D * 2;
-    // prefix conditioning into the first Lc positions of every row (model.py:184-186)
-    if (Lc > 0) {
-        hipError_t e = hipMemcpy2DAsync(d->x, S * row, cond, Lc * row, Lc * row, R, hipMemcpyDeviceToDevice,
-                                        (hipStream_t)stream);
-        if (e != hipSuccess) {
-            zk_set_error("zk_prefill: conditioning copy: %s", hipGetErrorString(e));
-            return -1;
-        }
-    }
-    ZK_STEP(zk_embed_codes(d->st.delayed, B, P + 1, K, (long)d->st.Ld * K, d->st.Ld, nullptr, 0, d->emb, V, D, 2,
-                           d->x, S, Lc, nullptr, nullptr, d->eps, nullptr, nullptr, stream));
-    ZK_STEP(zk_layernorm(d->x, d->layers[0].ln1_w, d->layers[0].ln1_b, d->eps, M, D, d->xn, stream));
-    for (int i = 0; i < d->n_layer; ++i) {
-        const zk_step_layer& L = d->layers[i];
-        ZK_STEP(zk_gemm_bf16(d->xn, D, L.wqkv, M, Nqkv, D, 1, 0, d->part, nullptr, nullptr, stream));
-        ZK_STEP(zk_qkv_rope(d->part, 1, R, S, H, Hk, hd, d->freqs, 0, nullptr, q, L.k_cache, L.vt_cache, d->smax,
-                            nullptr, d->rope_neox, nullptr, stream));
-        ZK_STEP(zk_attn_prefill(q, L.k_cache, L.vt_cache, R, S, H, Hk, hd, d->smax, d->y, stream));
-        ZK_STEP(zk_gemm_bf16(d->y, H * hd, L.wo, M, D, H * hd, 1, 0, d->part, nullptr, nullptr, stream));
-        ZK_STEP(zk_resid_ln(d->part, 1, d->x, L.ln2_w, L.ln2_b, d->eps, M, D, d->x, d->xn, 0, nullptr, stream));
-        ZK_STEP(zk_gemm_bf16(d->xn, D, L.fc1, M, 2 * Fd, D, 1, 1, nullptr, d->h, nullptr, stream));
-        ZK_STEP(zk_gemm_bf16(d->h, Fd, L.fc2, M, D, Fd, 1, 0, d->part, nullptr, nullptr, stream));
-        const bool last = i + 1 == d->n_layer;
-        ZK_STEP(zk_resid_ln(d->part, 1, d->x, last ? d->lnf_w : d->layers[i + 1].ln1_w,
-                            last ? d->lnf_b : d->layers[i + 1].ln1_b, d->eps, M, D, d->x, d->xn, 0, nullptr, stream));
-    }
-    // heads on the last position of every row (rows r*S + S-1 via lda = S*D)
-    ZK_STEP(zk_gemm_bf16(static_cast<const char*>(d->xn) + (size_t)(S - 1) * row, (long)S * D, d->heads, R, K * V, D,
-                         d->split_heads, 0, d->part, nullptr, nullptr, stream));
-    ZK_STEP(zk_sample_heads(d->part, d->split_heads, &d->st, &d->sp, 1, 0, d->dbg, stream));
-    ZK_STEP(zk_eos_step(&d->st, 1, P + 1, stream));
-    return 0;
+    ZK_STEP(prefill_prologue("zk_prefill", step_ok(d), d, cond, Lc, P, q, stream));
+    const int R = 2 * d->B, S = Lc + P + 1;
+    ZK_STEP(zk_layernorm(d->x, d->layers[0].ln1_w, d->layers[0].ln1_b, d->eps, R * S, d->d_model, d->xn, stream));
+    ZK_STEP(transformer_layers(d, R, S, true, q, stream));
+    return prefill_epilogue(d, S, P, stream);
 }
 
 // ------------------------------------------------------------------ hybrid step (zonos_amd.hybrid)
@@ -310,11 +344,10 @@ int hybrid_layers(const zk_hybrid_desc* d, int R, int S, bool prefill, void* q, 
         zk_set_error("zk_hybrid: residual_in_fp32 needs the fp32 residual buffer xf");
         return -1;
     }
-    const ZkWarm none{nullptr, 0, 0, 0, 0};
     // L2 warm-up (warm.h) of the GEMM that follows layer i's last k_resid_ln: the next layer's first
     // GEMM, or the heads
     auto next_warm = [&](int i) {
-        if (prefill) return none;
+        if (prefill) return kNoWarm;
         if (i + 1 == d->n_layer) return warm_desc(d->heads, M, K * V, D, d->split_heads);
         const zk_hybrid_layer& N1 = d->layers[i + 1];
         return N1.type == 0 ? warm_desc(N1.wqkv, M, Nqkv, D, sq) : warm_desc(N1.w_in, M, nin, D, si);
@@ -362,9 +395,9 @@ int hybrid_layers(const zk_hybrid_desc* d, int R, int S, bool prefill, void* q, 
         if (Fl > 0) {
             const int sfl = prefill ? 1 : fit_split(Fl, sf);
             ZK_STEP(zk_resid_ln_warm(d->part, smix, xr, L.ln2_w, L.ln2_b, d->eps, M, D, xr, d->xn, rf, skip,
-                                     prefill ? none : warm_desc(L.fc1, M, 2 * Fl, D, 1, 1), stream));
+                                     prefill ? kNoWarm : warm_desc(L.fc1, M, 2 * Fl, D, 1, 1), stream));
             ZK_STEP(zk_gemm_bf16_warm(d->xn, D, L.fc1, M, 2 * Fl, D, 1, 1, nullptr, d->h, skip,
-                                      prefill ? none : warm_desc(L.fc2, M, D, Fl, sfl), stream));
+                                      prefill ? kNoWarm : warm_desc(L.fc2, M, D, Fl, sfl), stream));
             ZK_STEP(zk_gemm_bf16(d->h, Fl, L.fc2, M, D, Fl, sfl, 0, d->part, nullptr, skip, stream));
             smix = sfl;
         }
@@ -389,43 +422,18 @@ extern "C" int zk_hybrid_decode_step(const zk_hybrid_desc* d, void* stream) {
     if (var) ZK_STEP(hybrid_prenorm(d, R, skip, stream));
     ZK_STEP(hybrid_layers(d, R, 1, false, nullptr, stream));
     ZK_STEP(zk_gemm_bf16(d->xn, D, d->heads, R, K * V, D, d->split_heads, 0, d->part, nullptr, skip, stream));
-    ZK_STEP(zk_sample_heads(d->part, d->split_heads, &d->st, &d->sp, 0, 0, d->dbg, stream));
-    ZK_STEP(zk_sample_heads(d->part, d->split_heads, &d->st, &d->sp, 0, 1, nullptr, stream));
-    ZK_STEP(zk_eos_step(&d->st, 0, 0, stream));
-    return 0;
+    return decode_tail(d, d->split_heads, stream);
 }
 
 extern "C" int zk_hybrid_prefill(const zk_hybrid_desc* d, const void* cond, int Lc, int P, void* q, void* stream) {
-    if (!hybrid_ok(d) || cond == nullptr || q == nullptr || Lc < 0 || P < 0) {
-        zk_set_error("zk_hybrid_prefill: bad arguments");
-        return -1;
-    }
-    if (Lc + d->st.Ld > d->smax) {     // as zk_prefill: no real step may need the attention's clamp
-        zk_set_error("zk_hybrid_prefill: KV cache of %d keys is shorter than Lc + Ld = %d", d->smax, Lc + d->st.Ld);
-        return -1;
-    }
-    const int K = d->st.K, V = d->st.V, B = d->B, R = 2 * B, S = Lc + P + 1, D = d->d_model;
-    const size_t row = (size_t)D * 2;
-    if (Lc > 0) {
-        hipError_t e = hipMemcpy2DAsync(d->x, S * row, cond, Lc * row, Lc * row, R, hipMemcpyDeviceToDevice,
-                                        (hipStream_t)stream);
-        if (e != hipSuccess) {
-            zk_set_error("zk_hybrid_prefill: conditioning copy: %s", hipGetErrorString(e));
-            return -1;
-        }
-    }
-    ZK_STEP(zk_embed_codes(d->st.delayed, B, P + 1, K, (long)d->st.Ld * K, d->st.Ld, nullptr, 0, d->emb, V, D, 2,
-                           d->x, S, Lc, nullptr, nullptr, d->eps, nullptr, nullptr, stream));
+    ZK_STEP(prefill_prologue("zk_hybrid_prefill", hybrid_ok(d), d, cond, Lc, P, q, stream));
+    const int R = 2 * d->B, S = Lc + P + 1, D = d->d_model;
     if (d->norm_flags & 6) ZK_STEP(hybrid_prenorm(d, R * S, nullptr, stream));
     else ZK_STEP(zk_layernorm(d->x, d->layers[0].ln1_w, d->layers[0].ln1_b, d->eps, R * S, D, d->xn, stream));
     ZK_STEP(hybrid_layers(d, R, S, true, q, stream));
-    ZK_STEP(zk_gemm_bf16(static_cast<const char*>(d->xn) + (size_t)(S - 1) * row, (long)S * D, d->heads, R, K * V, D,
-                         d->split_heads, 0, d->part, nullptr, nullptr, stream));
-    ZK_STEP(zk_sample_heads(d->part, d->split_heads, &d->st, &d->sp, 1, 0, d->dbg, stream));
-    ZK_STEP(zk_eos_step(&d->st, 1, P + 1, stream));
-    return 0;
+    return prefill_epilogue(d, S, P, stream);
 }
-#undef ZK_STEP
+
 
 // ------------------------------------------------------------------ DAC decode (whole)
 namespace {
@@ -461,11 +469,6 @@ extern "C" size_t zk_dac_decode_workspace(const zk_dac_desc* d, int B, int T) {
     return dac_plan(d, B, T, p) ? p.total : 0;
 }
 
-#define ZK_DSTEP(call)                 \
-    do {                               \
-        if ((call) != 0) return -1;    \
-    } while (0)
-
 extern "C" int zk_dac_decode(const zk_dac_desc* d, const int64_t* codes, int B, int T, const int32_t* lens,
                              void* workspace, size_t workspace_bytes, float* out, void* stream) {
     DacPlan p;
@@ -490,11 +493,11 @@ extern "C" int zk_dac_decode(const zk_dac_desc* d, const int64_t* codes, int B, 
     };
     float* x = reinterpret_cast<float*>(ws + p.x);
     float* last_act = reinterpret_cast<float*>(ws + p.last);
-    ZK_DSTEP(zk_dac_rvq_decode_cl(codes, B, d->ncb, T, (long)d->ncb * T, d->tables, d->codebook_size, d->hidden,
-                                  d->cin0, z, lens, stream));
+    ZK_STEP(zk_dac_rvq_decode_cl(codes, B, d->ncb, T, (long)d->ncb * T, d->tables, d->codebook_size, d->hidden,
+                                 d->cin0, z, lens, stream));
     const float* a_next = d->nblocks ? d->blocks[0].alpha : d->final_alpha;
-    ZK_DSTEP(zk_dac_conv_cl(z, B, d->cin0, T, d->conv1_w, 0, d->conv1_b, d->c0, 7, 1, 3, T, 1, 1, 0, T, nullptr,
-                            nullptr, a_next, bufs[0], 0, lens, 1, 1, stream));
+    ZK_STEP(zk_dac_conv_cl(z, B, d->cin0, T, d->conv1_w, 0, d->conv1_b, d->c0, 7, 1, 3, T, 1, 1, 0, T, nullptr,
+                           nullptr, a_next, bufs[0], 0, lens, 1, 1, stream));
     int L = T, scale = 1, cch = d->c0;
     const void* act = bufs[0];
     bool act_f32 = false;
@@ -502,9 +505,9 @@ extern "C" int zk_dac_decode(const zk_dac_desc* d, const int64_t* codes, int B, 
         const zk_dac_block& k = d->blocks[bi];
         const int st = k.stride, Lo = L * st;
         uint16_t* s_new = other(act, nullptr);
-        ZK_DSTEP(zk_dac_conv_cl(static_cast<const uint16_t*>(act), B, k.cin, L, k.wt, 2L * k.cout * k.cin, k.bt,
-                                k.cout, 2, 1, 1, L + 1, st, st, -((st + 1) / 2), Lo, nullptr, x, k.res[0].a1, s_new, 0,
-                                lens, scale, scale * st, stream));
+        ZK_STEP(zk_dac_conv_cl(static_cast<const uint16_t*>(act), B, k.cin, L, k.wt, 2L * k.cout * k.cin, k.bt,
+                               k.cout, 2, 1, 1, L + 1, st, st, -((st + 1) / 2), Lo, nullptr, x, k.res[0].a1, s_new, 0,
+                               lens, scale, scale * st, stream));
         act = s_new;
         scale *= st;
         L = Lo;
@@ -518,16 +521,16 @@ extern "C" int zk_dac_decode(const zk_dac_desc* d, const int64_t* codes, int B, 
             if (fm == 2 || (fm == 1 && !last)) {
                 // the whole unit in one launch (k7 -> Snake -> 1x1 -> + x -> next Snake)
                 void* s_out = last ? static_cast<void*>(last_act) : static_cast<void*>(tmp);
-                ZK_DSTEP(zk_dac_resunit_cl(static_cast<const uint16_t*>(act), B, k.cout, L, ru.w1, ru.b1, ru.dil,
-                                           ru.a2, ru.w2, ru.b2, x, an, s_out, last ? 1 : 0, lens, scale, stream));
+                ZK_STEP(zk_dac_resunit_cl(static_cast<const uint16_t*>(act), B, k.cout, L, ru.w1, ru.b1, ru.dil,
+                                          ru.a2, ru.w2, ru.b2, x, an, s_out, last ? 1 : 0, lens, scale, stream));
                 act = s_out;
             } else {
-                ZK_DSTEP(zk_dac_conv_cl(static_cast<const uint16_t*>(act), B, k.cout, L, ru.w1, 0, ru.b1, k.cout, 7,
-                                        ru.dil, 3 * ru.dil, L, 1, 1, 0, L, nullptr, nullptr, ru.a2, tmp, 0, lens,
-                                        scale, scale, stream));
+                ZK_STEP(zk_dac_conv_cl(static_cast<const uint16_t*>(act), B, k.cout, L, ru.w1, 0, ru.b1, k.cout, 7,
+                                       ru.dil, 3 * ru.dil, L, 1, 1, 0, L, nullptr, nullptr, ru.a2, tmp, 0, lens,
+                                       scale, scale, stream));
                 void* s_out = last ? static_cast<void*>(last_act) : const_cast<void*>(act);
-                ZK_DSTEP(zk_dac_conv_cl(tmp, B, k.cout, L, ru.w2, 0, ru.b2, k.cout, 1, 1, 0, L, 1, 1, 0, L, x, x, an,
-                                        s_out, last ? 1 : 0, lens, scale, scale, stream));
+                ZK_STEP(zk_dac_conv_cl(tmp, B, k.cout, L, ru.w2, 0, ru.b2, k.cout, 1, 1, 0, L, 1, 1, 0, L, x, x, an,
+                                       s_out, last ? 1 : 0, lens, scale, scale, stream));
                 act = s_out;
             }
             if (last) act_f32 = true;
@@ -538,8 +541,8 @@ extern "C" int zk_dac_decode(const zk_dac_desc* d, const int64_t* codes, int B, 
         zk_set_error("zk_dac_decode: the tail needs at least one block (fp32 Snake input)");
         return -1;
     }
-    ZK_DSTEP(zk_dac_tail_cl(static_cast<const float*>(act), B, cch, L, d->conv2_w, d->conv2_b, out, lens, scale,
-                            stream));
+    ZK_STEP(zk_dac_tail_cl(static_cast<const float*>(act), B, cch, L, d->conv2_w, d->conv2_b, out, lens, scale,
+                           stream));
     return 0;
 }
-#undef ZK_DSTEP
+#undef ZK_STEP

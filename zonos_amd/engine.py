@@ -18,6 +18,7 @@ Design (MI355X-first):
 """
 from __future__ import annotations
 
+import ctypes as C
 import logging
 import math
 from dataclasses import dataclass
@@ -114,6 +115,57 @@ def attn_merge_for(R: int, smax: int) -> int:
 ATTN_MERGE_DEFAULT = 4
 
 
+def decode_splits(c, R: int) -> dict:
+    """Split-K counts of the decode GEMMs over R rows (prefill runs every GEMM unsplit).
+    heads: no split-K (145 workgroups of 64 columns stream 37.8 MB in 15.6 us vs 19.8 us with 2
+    splits, tools/microbench.py gemm; the sampler then reads one slab). out_proj: 4-way split-K
+    (128 workgroups) is as fast as 8-way (6.6 vs 6.5 us) and halves the fp32 slabs it writes and
+    k_resid_ln reads (4.2 vs 8.4 MB; resid_ln 4.3 vs 4.8 us). fc2: of the attention MLP, or of the
+    hybrid's Mamba-block MLP (d_mlp) when there is no attention MLP."""
+    D, H, hd = c.d_model, c.n_heads, c.head_dim
+    return dict(qkv=_split_for((H + 2 * c.n_kv) * hd, D, R), o=_split_for(D, H * hd, R, target_blocks=128),
+                fc2=_split_for(D, c.d_ff or getattr(c, "d_mlp", 0) or 64, R), heads=1)
+
+
+def activation_buffers(c, dev, Mp: int, R: int, smax: int, splits: dict, attn_ways: int) -> dict:
+    """The buffers one pass of either backbone works in: a prefill over Mp rows (split-K 1) or a
+    decode step over R <= Mp rows under `splits`. part holds the fp32 slabs of whichever GEMM is
+    running: Mp rows unsplit or R rows x its split (the heads: R rows only); attn_work the partials
+    of attn_ways key splits. A hybrid config adds the fp32 residual (xf), the Mamba y * silu(z) /
+    gated-norm rows (yz, ym) and the prefill conv scratch (xc)."""
+    D, H, Hk, hd = c.d_model, c.n_heads, c.n_kv, c.head_dim
+    di, nin = getattr(c, "d_inner", 0), getattr(c, "d_in_proj", 0)
+    f32, bf = torch.float32, torch.bfloat16
+
+    def rows(*names):            # slab rows of the widest of these GEMMs
+        return max(Mp, *(splits.get(n, 0) * R for n in names))
+
+    part_n = max((H + 2 * Hk) * hd * rows("qkv"), D * rows("o", "fc2", "out"), nin * rows("inp"),
+                 N_CB * VOCAB * splits.get("heads", 0) * R)
+    ws = dict(x=torch.empty(Mp, D, dtype=bf, device=dev), xn=torch.empty(Mp, D, dtype=bf, device=dev),
+              q=torch.empty(Mp, H * hd, dtype=bf, device=dev), y=torch.empty(Mp, H * hd, dtype=bf, device=dev),
+              h=torch.empty(Mp, max(c.d_ff, getattr(c, "d_mlp", 0), 1), dtype=bf, device=dev),
+              part=torch.empty(part_n, dtype=f32, device=dev),
+              attn_work=torch.empty(max(1, R * Hk * attn_ways * (8 + 4 * hd)), dtype=f32, device=dev),
+              scal=torch.zeros(16, dtype=torch.int32, device=dev))
+    if di:
+        ws.update(xf=torch.empty(Mp, D, dtype=f32, device=dev) if c.residual_in_fp32 else None,
+                  yz=torch.empty(Mp, di, dtype=f32, device=dev), ym=torch.empty(Mp, di, dtype=bf, device=dev),
+                  xc=torch.empty(Mp, c.conv_dim, dtype=bf, device=dev))
+    return ws
+
+
+def generation_state(dev, B: int, Ld: int) -> dict:
+    """The device words of the generate() loop (zk_gen_state) and the sampler's logits copy."""
+    f32, i32 = torch.float32, torch.int32
+    return dict(eos_mode=torch.zeros(B, dtype=i32, device=dev), steps_after=torch.zeros(B, dtype=i32, device=dev),
+                remaining=torch.zeros(B, dtype=i32, device=dev), stopping=torch.zeros(B, dtype=i32, device=dev),
+                act=torch.zeros(B, dtype=i32, device=dev), rp=torch.ones(B, dtype=f32, device=dev),
+                tok0=torch.zeros(B * N_CB, dtype=i32, device=dev), tok1=torch.zeros(B * N_CB, dtype=i32, device=dev),
+                delayed=torch.empty(B, N_CB, Ld, dtype=torch.int64, device=dev),
+                dbg=torch.empty(B, N_CB, VOCAB, dtype=f32, device=dev))
+
+
 class HipBackbone:
     """The 26 transformer blocks + final LayerNorm on the device (zonos/backbone/_torch.py:52-152):
     bf16 weights in the engine's layouts and the layer launch sequence. Shared by the generate()
@@ -151,6 +203,9 @@ class HipBackbone:
         self.lnf_b = w("norm_f.bias")
         self.freqs = rope_table(16384, c.head_dim).to(dev)
 
+    def splits(self, R: int) -> dict:
+        return decode_splits(self.cfg, R)
+
     def _layers_small(self, ws, R: int, stream, skip):
         """Decode step of the 26 blocks for R <= 16 rows (B <= 8), five launches per block:
         [norm -> in_proj] -> attention (RoPE, KV write) -> [out_proj -> x += .] ->
@@ -172,24 +227,20 @@ class HipBackbone:
                      ptr(ws["attn_work"]), merge, skip, stream)
                 call("zk_gemv_attn_out", ptr(ws["attn_work"]), merge, Hk, ptr(L["wo"]), R, D, H * hd, ptr(x), skip,
                      stream)
-                call("zk_gemv_fused", ptr(x), D, ptr(L["fc1"]), R, 2 * Fd, D, 1, ptr(L["ln2_w"]), ptr(L["ln2_b"]),
-                     c.eps, None, ptr(h), skip, stream)
-                call("zk_gemv_fused", ptr(h), Fd, ptr(L["fc2"]), R, D, Fd, 2, None, None, c.eps, None, ptr(x), skip,
-                     stream)
-                continue
-            call("zk_gemv_fused", ptr(x), D, ptr(L["wqkv"]), R, Nqkv, D, 0, ptr(L["ln1_w"]), ptr(L["ln1_b"]), c.eps,
-                 ptr(part), None, skip, stream)
-            if merge:
-                call("zk_attn_decode_qkv_part", ptr(part), 1, ptr(self.freqs), ptr(kc), ptr(vt), R, H, Hk, hd,
-                     ws["smax"], 1, ptr(scal[1:2]), ptr(ws["attn_work"]), merge, self.rope_neox, skip, stream)
-                call("zk_gemv_attn_out", ptr(ws["attn_work"]), merge, Hk, ptr(L["wo"]), R, D, H * hd, ptr(x), skip,
-                     stream)
             else:
-                call("zk_attn_decode_qkv_sc", ptr(part), 1, ptr(self.freqs), ptr(kc), ptr(vt), R, H, Hk, hd,
-                     ws["smax"], 1, ptr(scal[1:2]), ptr(ws["attn_work"]), ws["attn_splits"], ptr(ws["attn_cnt"]),
-                     ptr(y), self.rope_neox, skip, stream)
-                call("zk_gemv_fused", ptr(y), H * hd, ptr(L["wo"]), R, D, H * hd, 2, None, None, c.eps, None,
-                     ptr(x), skip, stream)
+                call("zk_gemv_fused", ptr(x), D, ptr(L["wqkv"]), R, Nqkv, D, 0, ptr(L["ln1_w"]), ptr(L["ln1_b"]),
+                     c.eps, ptr(part), None, skip, stream)
+                if merge:
+                    call("zk_attn_decode_qkv_part", ptr(part), 1, ptr(self.freqs), ptr(kc), ptr(vt), R, H, Hk, hd,
+                         ws["smax"], 1, ptr(scal[1:2]), ptr(ws["attn_work"]), merge, self.rope_neox, skip, stream)
+                    call("zk_gemv_attn_out", ptr(ws["attn_work"]), merge, Hk, ptr(L["wo"]), R, D, H * hd, ptr(x),
+                         skip, stream)
+                else:
+                    call("zk_attn_decode_qkv_sc", ptr(part), 1, ptr(self.freqs), ptr(kc), ptr(vt), R, H, Hk, hd,
+                         ws["smax"], 1, ptr(scal[1:2]), ptr(ws["attn_work"]), ws["attn_splits"],
+                         ptr(ws["attn_cnt"]), ptr(y), self.rope_neox, skip, stream)
+                    call("zk_gemv_fused", ptr(y), H * hd, ptr(L["wo"]), R, D, H * hd, 2, None, None, c.eps, None,
+                         ptr(x), skip, stream)
             call("zk_gemv_fused", ptr(x), D, ptr(L["fc1"]), R, 2 * Fd, D, 1, ptr(L["ln2_w"]), ptr(L["ln2_b"]),
                  c.eps, None, ptr(h), skip, stream)
             call("zk_gemv_fused", ptr(h), Fd, ptr(L["fc2"]), R, D, Fd, 2, None, None, c.eps, None, ptr(x), skip,
@@ -255,14 +306,17 @@ class HipDecoder(HipBackbone):
 
     def __init__(self, cfg: EngineConfig, weights: dict, device="cuda"):
         super().__init__(cfg, weights, device)
-        c = cfg
+        self._load_io(weights)
+
+    def _load_io(self, weights: dict):
+        """The 9 embedding tables stacked and the 9 heads stacked + packed (model.py:97-111)."""
         dev = self.device
 
         def w(name):
             return weights[name].to(device=dev, dtype=torch.bfloat16).contiguous()
 
         self.emb = torch.stack([w(f"embeddings.{k}.weight") for k in range(N_CB)]).contiguous()
-        assert self.emb.shape == (N_CB, VOCAB, c.d_model), self.emb.shape
+        assert self.emb.shape == (N_CB, VOCAB, self.cfg.d_model), self.emb.shape
         heads = []
         for k in range(N_CB):
             h = w(f"heads.{k}.weight")
@@ -274,9 +328,13 @@ class HipDecoder(HipBackbone):
         torch.cuda.synchronize(dev)
 
     # ------------------------------------------------------------------ workspace
+    def _new_state(self, R: int, smax: int) -> dict:
+        """What a generate() call starts from zeroed: the KV caches and the in-launch split-combine tickets."""
+        c, dev = self.cfg, self.device
+        return dict(kv=torch.zeros(c.n_layer, 2, R * c.n_kv * smax * c.head_dim, dtype=torch.bfloat16, device=dev),
+                    attn_cnt=torch.zeros(R * c.n_kv, dtype=torch.int32, device=dev))
+
     def _alloc(self, B: int, Lc: int, P: int, max_new: int):
-        c = self.cfg
-        dev = self.device
         R = 2 * B
         T = P + max_new
         Ld = T + N_CB
@@ -286,44 +344,18 @@ class HipDecoder(HipBackbone):
         key = (B, Lc, P, max_new)
         if self._ws is not None and self._ws["key"] == key:
             ws = self._ws
-            ws["kv"].zero_()
-            ws["attn_cnt"].zero_()
+            for k in ws["state_keys"]:
+                ws[k].zero_()
             return ws
         self.release()
-        D, H, Hk, hd, Fd = c.d_model, c.n_heads, c.n_kv, c.head_dim, c.d_ff
-        Nqkv = (H + 2 * Hk) * hd
-        Nh = N_CB * VOCAB
-        Mp = R * S_pre
-        f32, bf, i32 = torch.float32, torch.bfloat16, torch.int32
-        # heads: no split-K (145 workgroups of 64 columns stream 37.8 MB in 15.6 us vs 19.8 us
-        # with 2 splits, tools/microbench.py gemm; the sampler then reads one slab)
-        # out_proj: 4-way split-K (128 workgroups) is as fast as 8-way (6.6 vs 6.5 us) and halves
-        # the fp32 slabs it writes and k_resid_ln reads (4.2 vs 8.4 MB; resid_ln 4.3 vs 4.8 us)
-        splits = dict(qkv=_split_for(Nqkv, D, R), o=_split_for(D, H * hd, R, target_blocks=128),
-                      fc2=_split_for(D, Fd, R), heads=1)
-        part_n = max(Mp * Nqkv, Mp * D, splits["qkv"] * R * Nqkv, splits["o"] * R * D, splits["fc2"] * R * D,
-                     splits["heads"] * R * Nh)
-        attn_splits = attn_splits_for(R, Hk, smax)
-        attn_merge = attn_merge_for(R, smax)
-        ws = dict(
-            key=key, R=R, T=T, Ld=Ld, smax=smax, S_pre=S_pre, splits=splits, attn_splits=attn_splits,
-            attn_merge=attn_merge,
-            kv=torch.zeros(c.n_layer, 2, R * Hk * smax * hd, dtype=bf, device=dev),
-            x=torch.empty(Mp, D, dtype=bf, device=dev), xn=torch.empty(Mp, D, dtype=bf, device=dev),
-            q=torch.empty(Mp, H * hd, dtype=bf, device=dev), y=torch.empty(Mp, H * hd, dtype=bf, device=dev),
-            h=torch.empty(Mp, Fd, dtype=bf, device=dev), part=torch.empty(part_n, dtype=f32, device=dev),
-            attn_work=torch.empty(max(1, R * Hk * max(attn_splits, attn_merge) * (8 + 4 * hd)), dtype=f32,
-                                  device=dev),
-            attn_cnt=torch.zeros(R * Hk, dtype=i32, device=dev),     # in-launch split-combine tickets
-            scal=torch.zeros(16, dtype=i32, device=dev),
-            eos_mode=torch.zeros(B, dtype=i32, device=dev), steps_after=torch.zeros(B, dtype=i32, device=dev),
-            remaining=torch.zeros(B, dtype=i32, device=dev), stopping=torch.zeros(B, dtype=i32, device=dev),
-            act=torch.zeros(B, dtype=i32, device=dev), rp=torch.ones(B, dtype=f32, device=dev),
-            tok0=torch.zeros(B * N_CB, dtype=i32, device=dev), tok1=torch.zeros(B * N_CB, dtype=i32, device=dev),
-            delayed=torch.empty(B, N_CB, Ld, dtype=torch.int64, device=dev),
-            dbg=torch.empty(B, N_CB, VOCAB, dtype=f32, device=dev),
-            graph=None,
-        )
+        splits = self.splits(R)
+        attn_splits = attn_splits_for(R, self.cfg.n_kv, smax)
+        attn_merge = attn_merge_for(R, smax)       # read by the small-batch path only
+        state = self._new_state(R, smax)
+        ws = dict(key=key, R=R, T=T, Ld=Ld, smax=smax, S_pre=S_pre, splits=splits, attn_splits=attn_splits,
+                  attn_merge=attn_merge, state_keys=tuple(state), graph=None, **state,
+                  **activation_buffers(self.cfg, self.device, R * S_pre, R, smax, splits, max(attn_splits, attn_merge)),
+                  **generation_state(self.device, B, Ld))
         self._ws = ws
         return ws
 
@@ -404,9 +436,9 @@ class HipDecoder(HipBackbone):
         else:
             self._layers(ws, R, R, 1, False, stream, skip)
             self._heads(ws, R, 1, stream, skip)
-        call("zk_sample_heads", ptr(logits), nsp, C_ref(st), C_ref(sp), 0, 0, ptr(ws["dbg"]), stream)
-        call("zk_sample_heads", ptr(logits), nsp, C_ref(st), C_ref(sp), 0, 1, None, stream)
-        call("zk_eos_step", C_ref(st), 0, 0, stream)
+        call("zk_sample_heads", ptr(logits), nsp, C.byref(st), C.byref(sp), 0, 0, ptr(ws["dbg"]), stream)
+        call("zk_sample_heads", ptr(logits), nsp, C.byref(st), C.byref(sp), 0, 1, None, stream)
+        call("zk_eos_step", C.byref(st), 0, 0, stream)
 
     def _small(self, R: int) -> bool:
         return self.small_batch_path and R <= 16 and self.cfg.d_model == 2048
@@ -500,9 +532,9 @@ class HipDecoder(HipBackbone):
                 self._prenorm(ws, R * S, stream, None)
             self._layers(ws, R * S, R, S, True, stream, None)
             self._heads(ws, R, S, stream, None)
-            call("zk_sample_heads", ptr(ws["part"]), ws["splits"]["heads"], C_ref(st), C_ref(sp), 1, 0,
+            call("zk_sample_heads", ptr(ws["part"]), ws["splits"]["heads"], C.byref(st), C.byref(sp), 1, 0,
                  ptr(ws["dbg"]), stream)
-            call("zk_eos_step", C_ref(st), 1, P + 1, stream)
+            call("zk_eos_step", C.byref(st), 1, P + 1, stream)
         if _after_prefill is not None:      # test hook (teacher forcing of the first frame)
             _after_prefill(ws["delayed"][..., P + 1:P + 2])
         # Debug logging. The sampler statistics need the logits of every step (one step per poll);
@@ -658,13 +690,6 @@ class HipDecoder(HipBackbone):
         ws["graph"] = g.value
         ws["_keep"] = (st, sp)
         return g.value
-
-
-import ctypes as C  # noqa: E402
-
-
-def C_ref(x):
-    return C.byref(x)
 
 
 def finalize(delayed: torch.Tensor, offset: int, P: int, stream) -> list:

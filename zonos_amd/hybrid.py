@@ -25,7 +25,7 @@ import torch
 
 from . import _lib
 from ._lib import call, ptr
-from .engine import ATTN_CHUNK, N_CB, VOCAB, HipDecoder, _split_for, attn_splits_for, pack_weights
+from .engine import HipDecoder, _split_for, decode_splits, pack_weights
 
 # split-K of the Mamba in_proj GEMM at decode (k_mamba_step reads the slabs: 1, 2 or 4); unsplit is fastest, again in
 # round 6 after the step-word change: 4.263-4.280 / 4.316-4.317 / 4.585-4.586 ms (profiles/r6_c5_inp_split_ab.txt)
@@ -194,27 +194,30 @@ class HybridBackbone:
         j = self.mamba_ids.index(layer)
         return ws["conv"][j], ws["ssm"][j]
 
+    def splits(self, R: int) -> dict:
+        """decode_splits plus the Mamba projections. in_proj (N = 8512, K = 2048) without split-K: 133
+        workgroups, no fp32 slab round trip for k_mamba_step (c5 decode step 4.67 vs 4.87 ms with 2 splits,
+        4.96 with 4; tools/c5_split_ab.sh; round 4 with 80-column split-2 workgroups: the GEMM 15.3 -> 12.8 us
+        alone, the step 4.34 -> 4.39 ms, profiles/r4s3_hyb_inp_split_ab.txt). The attention out_proj 4-way and
+        the heads unsplit, as the transformer engine: 4.645 vs 4.670 ms."""
+        c = self.cfg
+        return dict(decode_splits(c, R), inp=MAMBA_INP_SPLIT, out=_split_for(c.d_model, c.d_inner, R))
+
     # ------------------------------------------------------------------ layer loop
     def _layers(self, ws, M: int, R: int, S: int, prefill: bool, stream, skip):
+        """The block sequence of capi.cpp hybrid_layers over M = R*S rows, xn -> xn (the norm of the next
+        block, or norm_f): the mixer through its output projection, the block's MLP if it has one
+        (attention blocks; Mamba blocks with d_mlp), each closed by a fused add + norm."""
         c = self.cfg
-        D, H, Hk, hd, Fd = c.d_model, c.n_heads, c.n_kv, c.head_dim, c.d_ff
+        D, H, Hk, hd = c.d_model, c.n_heads, c.n_kv, c.head_dim
         di, nin, nh = c.d_inner, c.d_in_proj, c.nheads_ssm
         Nqkv = (H + 2 * Hk) * hd
         sp = ws["splits"] if not prefill else dict(qkv=1, o=1, fc2=1, inp=1, out=1)
-        x, xn, q, y, h, part = ws["x"], ws["xn"], ws["q"], ws["y"], ws["h"], ws["part"]
-        xr = ws["xf"] if c.residual_in_fp32 else x           # the residual stream
+        xn, q, y, h, part = ws["xn"], ws["q"], ws["y"], ws["h"], ws["part"]
+        xr = ws["xf"] if c.residual_in_fp32 else ws["x"]     # the residual stream
         rf = c.resid_flags
-        scal = ws["scal"]
-        pos_dev = None if prefill else ptr(scal[1:2])
+        pos_dev = None if prefill else ptr(ws["scal"][1:2])
         for i, L in enumerate(self.layers):
-            if i + 1 < len(self.layers):
-                nw, nb = self.layers[i + 1]["ln1_w"], self.layers[i + 1]["ln1_b"]
-            else:
-                nw, nb = self.lnf_w, self.lnf_b
-            if c.norm_flags or c.d_mlp:
-                # the same sequence as zk_hybrid_decode_step's (capi.cpp hybrid_layers) for the variants
-                self._layer_var(ws, i, L, M, R, S, prefill, stream, skip, sp, xr, rf, nw, nb, pos_dev)
-                continue
             if L["type"] == "attn":
                 kc, vt = self._kv(ws, i)
                 call("zk_gemm_bf16", ptr(xn), D, ptr(L["wqkv"]), M, Nqkv, D, sp["qkv"], 0, ptr(part), None, skip,
@@ -225,84 +228,41 @@ class HybridBackbone:
                     call("zk_attn_prefill", ptr(q), ptr(kc), ptr(vt), R, S, H, Hk, hd, ws["smax"], ptr(y), stream)
                 else:
                     call("zk_attn_decode_qkv", ptr(part), sp["qkv"], ptr(self.freqs), ptr(kc), ptr(vt), R, H, Hk, hd,
-                         ws["smax"], 1, ptr(scal[1:2]), ptr(ws["attn_work"]), ws["attn_splits"], ptr(y), 1, skip,
-                         stream)
+                         ws["smax"], 1, pos_dev, ptr(ws["attn_work"]), ws["attn_splits"], ptr(y), 1, skip, stream)
                 call("zk_gemm_bf16", ptr(y), H * hd, ptr(L["wo"]), M, D, H * hd, sp["o"], 0, ptr(part), None, skip,
                      stream)
-                call("zk_resid_ln", ptr(part), sp["o"], ptr(x), ptr(L["ln2_w"]), ptr(L["ln2_b"]), c.eps, M, D,
-                     ptr(x), ptr(xn), 1, skip, stream)
-                call("zk_gemm_bf16", ptr(xn), D, ptr(L["fc1"]), M, 2 * Fd, D, 1, 1, None, ptr(h), skip, stream)
-                call("zk_gemm_bf16", ptr(h), Fd, ptr(L["fc2"]), M, D, Fd, sp["fc2"], 0, ptr(part), None, skip, stream)
-                call("zk_resid_ln", ptr(part), sp["fc2"], ptr(x), ptr(nw), ptr(nb), c.eps, M, D, ptr(x), ptr(xn), 1,
-                     skip, stream)
+                smix = sp["o"]
             else:
-                conv, ssm = self._states(ws, i)
-                # SSM state double-buffered by position parity
-                sr = S & 1
-                ssm_b = ptr(ssm[1])
+                conv, ssm = self._states(ws, i)      # each double-buffered by position parity
                 call("zk_gemm_bf16", ptr(xn), D, ptr(L["w_in"]), M, nin, D, sp["inp"], 0, ptr(part), None, skip,
                      stream)
                 if prefill:
-                    # the first decode step (position S) reads conv buffer (S & 1)
+                    # the first decode step (position S) reads the parity-(S & 1) buffers
                     call("zk_mamba_prefill", ptr(part), R, S, di, nh, c.headdim, c.d_state, ptr(L["conv_w"]),
-                         ptr(L["conv_b"]), ptr(ws["xc"]), ptr(conv[S & 1]), ptr(ssm[sr]), ptr(L["A"]),
-                         ptr(L["dt_bias"]),
-                         ptr(L["D"]), ptr(ws["yz"]), stream)
+                         ptr(L["conv_b"]), ptr(ws["xc"]), ptr(conv[S & 1]), ptr(ssm[S & 1]), ptr(L["A"]),
+                         ptr(L["dt_bias"]), ptr(L["D"]), ptr(ws["yz"]), stream)
                 else:
                     call("zk_mamba_step", ptr(part), sp["inp"], R, di, nh, c.headdim, c.d_state, ptr(L["conv_w"]),
-                         ptr(L["conv_b"]), ptr(conv[0]), ptr(conv[1]), pos_dev, ptr(ssm[0]), ssm_b, ptr(L["A"]),
+                         ptr(L["conv_b"]), ptr(conv[0]), ptr(conv[1]), pos_dev, ptr(ssm[0]), ptr(ssm[1]), ptr(L["A"]),
                          ptr(L["dt_bias"]), ptr(L["D"]), ptr(ws["yz"]), skip, stream)
                 call("zk_gated_rmsnorm", ptr(ws["yz"]), M, di, ptr(L["norm_w"]), 1e-5, ptr(ws["ym"]), skip, stream)
                 call("zk_gemm_bf16", ptr(ws["ym"]), di, ptr(L["w_out"]), M, D, di, sp["out"], 0, ptr(part), None,
                      skip, stream)
-                call("zk_resid_ln", ptr(part), sp["out"], ptr(x), ptr(nw), ptr(nb), c.eps, M, D, ptr(x), ptr(xn), 1,
-                     skip, stream)
-
-
-    def _layer_var(self, ws, i, L, M, R, S, prefill, stream, skip, sp, xr, rf, nw, nb, pos_dev):
-        """One block under rms_norm / residual_in_fp32 / a Mamba-block MLP (capi.cpp hybrid_layers)."""
-        c = self.cfg
-        D, H, Hk, hd = c.d_model, c.n_heads, c.n_kv, c.head_dim
-        di, nin, nh = c.d_inner, c.d_in_proj, c.nheads_ssm
-        Nqkv = (H + 2 * Hk) * hd
-        xn, q, y, h, part = ws["xn"], ws["q"], ws["y"], ws["h"], ws["part"]
-        if L["type"] == "attn":
-            kc, vt = self._kv(ws, i)
-            call("zk_gemm_bf16", ptr(xn), D, ptr(L["wqkv"]), M, Nqkv, D, sp["qkv"], 0, ptr(part), None, skip, stream)
-            if prefill:
-                call("zk_qkv_rope", ptr(part), 1, R, S, H, Hk, hd, ptr(self.freqs), 0, None, ptr(q), ptr(kc), ptr(vt),
-                     ws["smax"], None, 1, skip, stream)
-                call("zk_attn_prefill", ptr(q), ptr(kc), ptr(vt), R, S, H, Hk, hd, ws["smax"], ptr(y), stream)
+                smix = sp["out"]
+            Fl = L["d_mlp"]
+            if Fl:
+                sfl = fit_split(Fl, sp["fc2"])
+                call("zk_resid_ln", ptr(part), smix, ptr(xr), ptr(L["ln2_w"]), ptr(L["ln2_b"]), c.eps, M, D, ptr(xr),
+                     ptr(xn), rf, skip, stream)
+                call("zk_gemm_bf16", ptr(xn), D, ptr(L["fc1"]), M, 2 * Fl, D, 1, 1, None, ptr(h), skip, stream)
+                call("zk_gemm_bf16", ptr(h), Fl, ptr(L["fc2"]), M, D, Fl, sfl, 0, ptr(part), None, skip, stream)
+                smix = sfl
+            if i + 1 < len(self.layers):
+                nw, nb = self.layers[i + 1]["ln1_w"], self.layers[i + 1]["ln1_b"]
             else:
-                call("zk_attn_decode_qkv", ptr(part), sp["qkv"], ptr(self.freqs), ptr(kc), ptr(vt), R, H, Hk, hd,
-                     ws["smax"], 1, pos_dev, ptr(ws["attn_work"]), ws["attn_splits"], ptr(y), 1, skip, stream)
-            call("zk_gemm_bf16", ptr(y), H * hd, ptr(L["wo"]), M, D, H * hd, sp["o"], 0, ptr(part), None, skip, stream)
-            smix = sp["o"]
-        else:
-            conv, ssm = self._states(ws, i)
-            call("zk_gemm_bf16", ptr(xn), D, ptr(L["w_in"]), M, nin, D, sp["inp"], 0, ptr(part), None, skip, stream)
-            if prefill:
-                call("zk_mamba_prefill", ptr(part), R, S, di, nh, c.headdim, c.d_state, ptr(L["conv_w"]),
-                     ptr(L["conv_b"]), ptr(ws["xc"]), ptr(conv[S & 1]), ptr(ssm[S & 1]), ptr(L["A"]),
-                     ptr(L["dt_bias"]), ptr(L["D"]), ptr(ws["yz"]), stream)
-            else:
-                call("zk_mamba_step", ptr(part), sp["inp"], R, di, nh, c.headdim, c.d_state, ptr(L["conv_w"]),
-                     ptr(L["conv_b"]), ptr(conv[0]), ptr(conv[1]), pos_dev, ptr(ssm[0]), ptr(ssm[1]), ptr(L["A"]),
-                     ptr(L["dt_bias"]), ptr(L["D"]), ptr(ws["yz"]), skip, stream)
-            call("zk_gated_rmsnorm", ptr(ws["yz"]), M, di, ptr(L["norm_w"]), 1e-5, ptr(ws["ym"]), skip, stream)
-            call("zk_gemm_bf16", ptr(ws["ym"]), di, ptr(L["w_out"]), M, D, di, sp["out"], 0, ptr(part), None, skip,
+                nw, nb = self.lnf_w, self.lnf_b
+            call("zk_resid_ln", ptr(part), smix, ptr(xr), ptr(nw), ptr(nb), c.eps, M, D, ptr(xr), ptr(xn), rf, skip,
                  stream)
-            smix = sp["out"]
-        Fl = L["d_mlp"]
-        if Fl:
-            sfl = fit_split(Fl, sp["fc2"])
-            call("zk_resid_ln", ptr(part), smix, ptr(xr), ptr(L["ln2_w"]), ptr(L["ln2_b"]), c.eps, M, D, ptr(xr),
-                 ptr(xn), rf, skip, stream)
-            call("zk_gemm_bf16", ptr(xn), D, ptr(L["fc1"]), M, 2 * Fl, D, 1, 1, None, ptr(h), skip, stream)
-            call("zk_gemm_bf16", ptr(h), Fl, ptr(L["fc2"]), M, D, Fl, sfl, 0, ptr(part), None, skip, stream)
-            smix = sfl
-        call("zk_resid_ln", ptr(part), smix, ptr(xr), ptr(nw), ptr(nb), c.eps, M, D, ptr(xr), ptr(xn), rf, skip,
-             stream)
 
     def _prenorm(self, ws, M: int, stream, skip):
         """The first block's norm of the embedding rows in ws["x"] under the config variants
@@ -332,84 +292,16 @@ class HybridDecoder(HybridBackbone, HipDecoder):
     def __init__(self, cfg: HybridEngineConfig, weights: dict, device="cuda"):
         HybridBackbone.__init__(self, cfg, weights, device)
         self.embed_norm = not cfg.norm_flags
-        dev, bf = self.device, torch.bfloat16
+        self._load_io(weights)
 
-        def w(name):
-            return weights[name].to(device=dev, dtype=bf).contiguous()
-
-        self.emb = torch.stack([w(f"embeddings.{k}.weight") for k in range(N_CB)]).contiguous()
-        heads = []
-        for k in range(N_CB):
-            h = w(f"heads.{k}.weight")
-            if h.shape[0] < VOCAB:
-                h = torch.cat([h, h.new_zeros(VOCAB - h.shape[0], h.shape[1])])
-            heads.append(h)
-        self.heads = pack_weights(torch.cat(heads).contiguous(), _lib.stream_ptr(dev))
-        self._ws = None
-        torch.cuda.synchronize(dev)
-
-    # ------------------------------------------------------------------ workspace
-    def _alloc(self, B: int, Lc: int, P: int, max_new: int) -> dict:
-        c = self.cfg
-        dev = self.device
-        R = 2 * B
-        T = P + max_new
-        Ld = T + N_CB
-        seq_len = Lc + T + N_CB
-        smax = -(-seq_len // ATTN_CHUNK) * ATTN_CHUNK
-        S_pre = Lc + P + 1
-        key = (B, Lc, P, max_new)
-        if self._ws is not None and self._ws["key"] == key:
-            ws = self._ws
-            ws["kv"].zero_()
-            ws["conv"].zero_()
-            ws["ssm"].zero_()
-            return ws
-        self.release()
-        D, H, Hk, hd, Fd = c.d_model, c.n_heads, c.n_kv, c.head_dim, c.d_ff
-        di, nin = c.d_inner, c.d_in_proj
-        Nqkv = (H + 2 * Hk) * hd
-        Nh = N_CB * VOCAB
-        Mp = R * S_pre
-        f32, bf, i32 = torch.float32, torch.bfloat16, torch.int32
-        # Mamba in_proj (N = 8512, K = 2048) without split-K: 133 workgroups, no fp32 slab round trip
-        # for k_mamba_step (c5 decode step 4.67 vs 4.87 ms with 2 splits, 4.96 with 4; tools/c5_split_ab.sh;
-        # round 4 with 80-column split-2 workgroups: the GEMM 15.3 -> 12.8 us alone, the step 4.34 -> 4.39 ms,
-        # profiles/r4s3_hyb_inp_split_ab.txt)
-        # (attention out_proj 4-way and the heads unsplit, as the transformer engine: 4.645 vs 4.670 ms)
-        splits = dict(qkv=_split_for(Nqkv, D, R), o=_split_for(D, H * hd, R, target_blocks=128),
-                      fc2=_split_for(D, max(Fd, 64), R), heads=1, inp=MAMBA_INP_SPLIT, out=_split_for(D, di, R))
-        part_n = max(Mp * Nqkv, Mp * D, Mp * nin, splits["qkv"] * R * Nqkv, splits["o"] * R * D,
-                     splits["fc2"] * R * D, splits["heads"] * R * Nh, splits["inp"] * R * nin, splits["out"] * R * D)
-        if c.d_mlp and not Fd:       # a Mamba-block MLP without attention MLPs: its own fc2 split
-            splits["fc2"] = _split_for(D, c.d_mlp, R)
-            part_n = max(part_n, splits["fc2"] * R * D)
-        attn_splits = attn_splits_for(R, Hk, smax)
+    def _new_state(self, R: int, smax: int) -> dict:
+        """KV caches of the attention layers; conv and SSM states of the Mamba layers, both double-buffered
+        by step parity (zk_mamba_step reads one, writes the other)."""
+        c, dev, bf = self.cfg, self.device, torch.bfloat16
         na, nm = len(self.attn_ids), len(self.mamba_ids)
-        ws = dict(
-            key=key, R=R, T=T, Ld=Ld, smax=smax, S_pre=S_pre, splits=splits, attn_splits=attn_splits,
-            kv=torch.zeros(max(na, 1), 2, R * Hk * smax * hd, dtype=bf, device=dev),
-            conv=torch.zeros(max(nm, 1), 2, R * c.conv_dim * 4, dtype=bf, device=dev),
-            # double-buffered by step parity like the conv state (zk_mamba_step reads one, writes the other)
-            ssm=torch.zeros(max(nm, 1), 2, R * c.nheads_ssm * c.headdim * c.d_state, dtype=bf, device=dev),
-            x=torch.empty(Mp, D, dtype=bf, device=dev), xn=torch.empty(Mp, D, dtype=bf, device=dev),
-            q=torch.empty(Mp, H * hd, dtype=bf, device=dev), y=torch.empty(Mp, H * hd, dtype=bf, device=dev),
-            h=torch.empty(Mp, max(Fd, c.d_mlp, 1), dtype=bf, device=dev), part=torch.empty(part_n, dtype=f32, device=dev),
-            xf=torch.empty(Mp, D, dtype=f32, device=dev) if c.residual_in_fp32 else None,
-            yz=torch.empty(Mp, di, dtype=f32, device=dev), ym=torch.empty(Mp, di, dtype=bf, device=dev),
-            xc=torch.empty(Mp, c.conv_dim, dtype=bf, device=dev),
-            attn_work=torch.empty(max(1, R * Hk * attn_splits * (8 + 4 * hd)), dtype=f32, device=dev),
-            scal=torch.zeros(16, dtype=i32, device=dev),
-            eos_mode=torch.zeros(B, dtype=i32, device=dev), steps_after=torch.zeros(B, dtype=i32, device=dev),
-            remaining=torch.zeros(B, dtype=i32, device=dev), stopping=torch.zeros(B, dtype=i32, device=dev),
-            act=torch.zeros(B, dtype=i32, device=dev), rp=torch.ones(B, dtype=f32, device=dev),
-            tok0=torch.zeros(B * N_CB, dtype=i32, device=dev), tok1=torch.zeros(B * N_CB, dtype=i32, device=dev),
-            delayed=torch.empty(B, N_CB, Ld, dtype=torch.int64, device=dev),
-            dbg=torch.empty(B, N_CB, VOCAB, dtype=f32, device=dev),
-            graph=None,
-        )
-        self._ws = ws
-        return ws
+        return dict(kv=torch.zeros(max(na, 1), 2, R * c.n_kv * smax * c.head_dim, dtype=bf, device=dev),
+                    conv=torch.zeros(max(nm, 1), 2, R * c.conv_dim * 4, dtype=bf, device=dev),
+                    ssm=torch.zeros(max(nm, 1), 2, R * c.nheads_ssm * c.headdim * c.d_state, dtype=bf, device=dev))
 
     # ------------------------------------------------------------------ C ABI descriptor
     def _step_desc(self, ws, B, st, sp):
