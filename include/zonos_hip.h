@@ -221,6 +221,34 @@ int zk_attn_decode_q_part(const void* q, const void* k_cache, const void* vt_cac
                           int hd, int Smax, int ctx0, const int32_t* ctx_dev, float* work, int nsplit,
                           const int32_t* skip, void* stream);
 
+/* ------------------------------------------------------------------ FP8 (e4m3fn) KV cache
+ * The same attention (F.scaled_dot_product_attention, _torch.py:136, over the cache kept by
+ * _update_kv_cache, _torch.py:33-49) with K and V stored as OCP e4m3fn bytes plus one power-of-two scale
+ * per (row, kv head, key) for K and one for V (byte b = 2^(b-127), uint8 [R][Hkv][Smax]). Layout and the
+ * exact scale rule: zonos_amd.kvlayout (K8: [R][Hkv][Smax/32][h 2][kp 2][lane 64][q 2][8], V8:
+ * [R][Hkv][Smax/32][dp 4][lane 64][q 2][8]). hd = 128, Smax % 128 == 0, interleaved RoPE only.
+ * Every entry returns the bits the bf16 entry of the same role returns on the dequantised cache.
+ *
+ * zk_kv_quantize_e4m3: keys [0, S) of a bf16 fragment-order cache pair of Smax_src keys per (row, kv
+ * head) (what zk_qkv_rope wrote during prefill, _torch.py:33-49) -> the FP8 cache of Smax keys and its
+ * scales; destination keys >= S are left untouched. */
+int zk_kv_quantize_e4m3(const void* k_src, const void* vt_src, int R, int Hkv, int hd, int S, int Smax_src,
+                        void* k8, void* v8, void* k_scale, void* v_scale, int Smax, void* stream);
+/* zk_attn_decode over the FP8 cache (replaces the same lines, _torch.py:64-65 / :136). */
+int zk_attn_decode_f8(const void* q, const void* k8, const void* v8, const void* k_scale, const void* v_scale,
+                      int R, int H, int Hkv, int hd, int Smax, int ctx0, const int32_t* ctx_dev, float* work,
+                      int nsplit, void* out, const int32_t* skip, void* stream);
+/* zk_attn_decode_qkv_sc over the FP8 cache (_torch.py:61-65 + apply_rotary_emb :18-30 + _update_kv_cache
+ * :33-49): reduces the in_proj slabs, applies the interleaved RoPE, quantises the new key and value (one
+ * amax over the 128 dims each), attends over keys [0, ctx) with the new key's dequantised values and
+ * stores its bytes and scale bytes. counters non-NULL and nsplit > 1: in-launch combine as _sc;
+ * otherwise the combine launch. = zk_qkv_rope at ctx - 1 into a bf16 scratch + the quantisation of
+ * that key + zk_attn_decode_f8, bit for bit. */
+int zk_attn_decode_qkv_f8(const float* part, int gemm_nsplit, const float* freqs, void* k8, void* v8,
+                          void* k_scale, void* v_scale, int R, int H, int Hkv, int hd, int Smax, int ctx0,
+                          const int32_t* ctx_dev, float* work, int nsplit, uint32_t* counters, void* out,
+                          const int32_t* skip, void* stream);
+
 /* ------------------------------------------------------------------ graphs and timing
  * The decode step is captured once into a hipGraph and replayed (the reference runs the
  * transformer step eagerly: model.py:138-142, 220-222). */
@@ -284,7 +312,10 @@ int zk_eos_step(const zk_gen_state* st, int prefill, int prefix_len, void* strea
  * rope_neox zk_gemv_fused + zk_attn_decode_qkv_part + zk_gemv_attn_out); small = 0: seven
  * (split-K zk_gemm_bf16 + zk_attn_decode_qkv_sc + zk_resid_ln). Every position/offset is read
  * from st.scal on the device, so one call is captured once into a hipGraph and replayed.
- * Replaces the per-token Python loop body of model.py:322-424 for a C/C++ host. */
+ * Replaces the per-token Python loop body of model.py:322-424 for a C/C++ host.
+ * kv_fp8 = 1 (opt-in FP8 KV cache; a zeroed field is the bf16 cache): the seven-launch sequence at any
+ * batch size with zk_attn_decode_qkv_f8 as the attention; together with small = 1, or with a layer whose
+ * scale pointers (zk_prefill: or the scratch pair) are missing, both entries fail before any launch. */
 typedef struct zk_step_layer {
     const void* ln1_w;    /* norm.weight / bias (bf16 [D]) */
     const void* ln1_b;
@@ -294,8 +325,11 @@ typedef struct zk_step_layer {
     const void* ln2_b;
     const void* fc1;      /* mlp.fc1 in zk_permute_fc1 order, packed */
     const void* fc2;      /* mlp.fc2, packed */
-    void* k_cache;        /* this layer's K / V^T cache (fragment order, Smax keys per (row, kv head)) */
+    void* k_cache;        /* this layer's K / V^T cache (fragment order, Smax keys per (row, kv head));
+                             kv_fp8: the e4m3fn byte caches K8 / V8 of zk_attn_decode_f8 */
     void* vt_cache;
+    void* k_scale;        /* kv_fp8 only: the scale bytes uint8 [2B][n_kv][smax] of K and of V */
+    void* v_scale;
 } zk_step_layer;
 
 typedef struct zk_step_desc {
@@ -303,6 +337,7 @@ typedef struct zk_step_desc {
     int32_t split_qkv, split_o, split_fc2, split_heads;   /* split-K counts (small = 0) */
     int32_t attn_splits, attn_merge, rope_neox, small;
     float eps;
+    int32_t kv_fp8;                /* 0: bf16 KV cache; 1: FP8 (e4m3fn) cache, small must be 0 (below) */
     const zk_step_layer* layers;   /* [n_layer] */
     const void* emb;               /* codebook embeddings bf16 [9][1026][D] */
     const void* heads;             /* 9 heads stacked, packed */
@@ -319,6 +354,12 @@ typedef struct zk_step_desc {
     float* dbg;                    /* nullable: fp32 CFG logits of draw 0 */
     zk_gen_state st;
     zk_sampling_params sp;
+    /* kv_fp8 only, read by zk_prefill: one bf16 fragment-order K / V^T scratch pair of pre_smax keys per
+     * (row, kv head) (pre_smax % 32 == 0, >= S), reused by every layer: zk_qkv_rope and zk_attn_prefill
+     * run on it unchanged, then zk_kv_quantize_e4m3 fills the layer's FP8 cache. */
+    void* pre_k;
+    void* pre_vt;
+    int32_t pre_smax;
 } zk_step_desc;
 
 int zk_decode_step(const zk_step_desc* d, void* stream);

@@ -38,16 +38,17 @@ class GenState(C.Structure):
 
 class StepLayer(C.Structure):
     _fields_ = [("ln1_w", P), ("ln1_b", P), ("wqkv", P), ("wo", P), ("ln2_w", P), ("ln2_b", P), ("fc1", P),
-                ("fc2", P), ("k_cache", P), ("vt_cache", P)]
+                ("fc2", P), ("k_cache", P), ("vt_cache", P), ("k_scale", P), ("v_scale", P)]
 
 
 class StepDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("B", "n_layer", "d_model", "n_heads", "n_kv", "head_dim", "d_ff", "smax",
                                          "split_qkv", "split_o", "split_fc2", "split_heads", "attn_splits",
                                          "attn_merge", "rope_neox", "small")] + \
-              [("eps", F), ("layers", P), ("emb", P), ("heads", P), ("lnf_w", P), ("lnf_b", P), ("freqs", P),
-               ("x", P), ("xn", P), ("y", P), ("h", P), ("part", P), ("attn_work", P), ("attn_cnt", P), ("dbg", P),
-               ("st", GenState), ("sp", SamplingParams)]
+              [("eps", F), ("kv_fp8", C.c_int32), ("layers", P), ("emb", P), ("heads", P), ("lnf_w", P), ("lnf_b", P),
+               ("freqs", P), ("x", P), ("xn", P), ("y", P), ("h", P), ("part", P), ("attn_work", P), ("attn_cnt", P),
+               ("dbg", P), ("st", GenState), ("sp", SamplingParams), ("pre_k", P), ("pre_vt", P),
+               ("pre_smax", C.c_int32)]
 
 
 class HybridLayer(C.Structure):
@@ -106,6 +107,9 @@ _SIGS = {
     "zk_attn_decode_qkv": [P, I, P, P, P, I, I, I, I, I, I, P, P, I, P, I, P, P],
     "zk_attn_decode_qkv_sc": [P, I, P, P, P, I, I, I, I, I, I, P, P, I, P, P, I, P, P],
     "zk_attn_decode_qkv_part": [P, I, P, P, P, I, I, I, I, I, I, P, P, I, I, P, P],
+    "zk_kv_quantize_e4m3": [P, P, I, I, I, I, I, P, P, P, P, I, P],
+    "zk_attn_decode_f8": [P, P, P, P, P, I, I, I, I, I, I, P, P, I, P, P, P],
+    "zk_attn_decode_qkv_f8": [P, I, P, P, P, P, P, I, I, I, I, I, I, P, P, I, P, P, P, P],
     "zk_gemv_attn_out": [P, I, I, P, I, I, I, P, P, P],
     "zk_gemv_qkv_rope": [P, P, I, I, I, I, P, P, F, P, P, P, I, P, P, P, P],
     "zk_attn_decode_q_part": [P, P, P, I, I, I, I, I, I, P, P, I, P, P],

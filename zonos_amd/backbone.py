@@ -98,6 +98,8 @@ class HipZonosBackbone(nn.Module):
 
     def allocate_inference_cache(self, batch_size: int, max_seqlen: int, dtype=torch.bfloat16):
         """_torch.py:64-71: one KV cache per layer, here in the engine layout (bf16 only)."""
+        if dtype in ("fp8", torch.float8_e4m3fn):
+            raise ValueError("the backbone plugin keeps a bf16 KV cache; the FP8 cache is generate(kv_dtype='fp8')")
         assert dtype == torch.bfloat16, "the HIP attention kernels read a bf16 cache"
         c = self.ecfg
         smax = -(-max_seqlen // ATTN_CHUNK) * ATTN_CHUNK

@@ -85,8 +85,12 @@ struct AttnState {
     f32x4 o[8];      // o[dt][i] = O^T[d = dt*16 + 4lg + i][head = ln]
 };
 
+// SC (FP8 cache, attn_f8.h): the fragments hold the unscaled e4m3 values and the per-key power-of-two
+// scales of the lane's keys 8lg .. 8lg+7 multiply the scores (sk, K) and the bf16-rounded p (sv, V) --
+// exact, so the numbers are those of the dequantised cache.
+template <bool SC = false>
 ZK_DEV void attn_step(AttnState& st, const KVFrag& f, const bf16x8* qf, int key_base, int ctx, float scale,
-                      int lg) {
+                      int lg, const float* sk = nullptr, const float* sv = nullptr) {
     f32x4 sacc[2];
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
@@ -101,9 +105,11 @@ ZK_DEV void attn_step(AttnState& st, const KVFrag& f, const bf16x8* qf, int key_
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int key = key_base + 8 * lg + 4 * h + i;
-            const float sv = key < ctx ? sacc[h][i] * scale : -INFINITY;
-            sacc[h][i] = sv;
-            mx = fmaxf(mx, sv);
+            float sc = sacc[h][i];
+            if constexpr (SC) sc *= sk[4 * h + i];
+            sc = key < ctx ? sc * scale : -INFINITY;
+            sacc[h][i] = sc;
+            mx = fmaxf(mx, sc);
         }
     mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
     mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
@@ -123,6 +129,12 @@ ZK_DEV void attn_step(AttnState& st, const KVFrag& f, const bf16x8* qf, int key_
     ps += __shfl_xor(ps, 32, 64);
     st.l = st.l * corr + ps;
     st.m = mn;
+    if constexpr (SC) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) sacc[h][i] *= sv[4 * h + i];
+    }
     const uint4 pa = make_uint4(pack2(sacc[0][0], sacc[0][1]), pack2(sacc[0][2], sacc[0][3]),
                                 pack2(sacc[1][0], sacc[1][1]), pack2(sacc[1][2], sacc[1][3]));
 #pragma unroll

@@ -1,0 +1,508 @@
+// Decode attention over the FP8 (OCP e4m3fn) KV cache and the quantiser that fills it after prefill
+// (included by backbone.hip). Same block / wave / merge structure as attn_decode_wg (attn_common.h): 128-key
+// blocks, 32 keys per wave, the same split rule and wave merge, the same mfma_f32_16x16x32_bf16 steps
+// (attn_step), so the result is bit for bit that of the bf16 kernel on the dequantised cache.
+//
+// Cache layout per (row, kv head), 32-key slices of 4 KB (zonos_amd.kvlayout), each lane's load 16 B:
+//   K8: [slice][h 2][kp 2][lane 64][q 2][8]  lane = 16*lg + ln holds key 8*(ln>>2) + 4h + (ln&3),
+//       dims 32*(2kp + q) + 8lg .. +8
+//   V8: [slice][dp 4][lane 64][q 2][8]       lane holds channel 16*(2dp + q) + ln, keys 8lg .. 8lg+7
+//   scales: uint8 [Smax] per (row, kv head) for K and for V, byte b = scale 2^(b - 127)
+// The bytes are converted to bf16 UNSCALED (exact); the power-of-two scales of the lane's 8 keys multiply
+// the scores (K) and the bf16-rounded p (V) inside attn_step<true>, which is exact as well.
+//
+// In bounds: every data load reads 16 B at slice * 4096 + j * 1024 + lane * 16 (j < 4, lane < 64), every
+// scale load 8 B at slice * 32 + 8 * lg (lg < 4), with slice clamped to [0, Smax / 32 - 1] by slice_of();
+// so all of them lie inside the (row, kv head) block of Smax * 128 data bytes / Smax scale bytes, for any
+// context word, split and wave, including the loads issued before the skip / context test.
+#pragma once
+#include "attn_common.h"
+
+namespace {
+
+typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
+
+// ------------------------------------------------------------------ layout and scale rule
+ZK_DEV size_t k8_off(int key, int c8) {      // dims 8*c8 .. 8*c8+7 of key (8 contiguous bytes)
+    const int o = key & 31, grp = o >> 3, h = (o >> 2) & 1, i = o & 3;
+    const int ln = 4 * grp + i, ks = c8 >> 2, lg = c8 & 3;
+    return (size_t)(key >> 5) * 4096 + ((h * 2 + (ks >> 1)) * 64 + lg * 16 + ln) * 16 + (ks & 1) * 8;
+}
+ZK_DEV size_t v8_off(int key, int ch) {      // channel ch of key
+    const int o = key & 31, lg = o >> 3, e = o & 7, dt = ch >> 4;
+    return (size_t)(key >> 5) * 4096 + ((dt >> 1) * 64 + lg * 16 + (ch & 15)) * 16 + (dt & 1) * 8 + e;
+}
+// amax = m * 2^x, m in [1, 2): e = x - 8 for m <= 1.75, else x - 7 (the smallest e with amax * 2^-e <= 448),
+// clamped to [-126, 127]; 0 for amax == 0 (kvlayout.kv_scale_exponent computes the same integer)
+ZK_DEV int kv_scale_exp(float amax) {
+    const uint32_t u = __float_as_uint(amax);
+    const int e = (int)(u >> 23) - 127 - 8 + ((u & 0x7fffffu) > 0x600000u ? 1 : 0);
+    return amax == 0.f ? 0 : max(-126, min(127, e));
+}
+ZK_DEV float kv_pow2(int e) { return __uint_as_float((uint32_t)(e + 127) << 23); }      // e in [-126, 127]
+// two / four e4m3fn bytes of x * inv, round to nearest even
+ZK_DEV uint32_t quant2(float a, float b, float inv) {
+    return (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(a * inv, b * inv, 0, false) & 0xffffu;
+}
+ZK_DEV uint32_t quant4(const float* f, float inv) {
+    int w = __builtin_amdgcn_cvt_pk_fp8_f32(f[0] * inv, f[1] * inv, 0, false);
+    w = __builtin_amdgcn_cvt_pk_fp8_f32(f[2] * inv, f[3] * inv, w, true);
+    return (uint32_t)w;
+}
+
+// ------------------------------------------------------------------ fragments
+struct KV8Frag {
+    uint4 k[2][2];   // [tile h][d-step pair]
+    uint4 v[4];      // [d-tile pair]
+    uint2 ks, vs;    // scale bytes of keys 8lg .. 8lg+7
+};
+
+template <bool NT>
+ZK_DEV void load_kv8(KV8Frag& f, const uint8_t* kb, const uint8_t* vb, const uint8_t* ksb, const uint8_t* vsb,
+                     int slice, int lane, int lg) {
+    const uint8_t* k0 = kb + (size_t)slice * 4096 + lane * 16;
+    const uint8_t* v0 = vb + (size_t)slice * 4096 + lane * 16;
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int kp = 0; kp < 2; ++kp) f.k[h][kp] = ld_kv<NT>(reinterpret_cast<const bf16_t*>(k0 + (h * 2 + kp) * 1024));
+#pragma unroll
+    for (int dp = 0; dp < 4; ++dp) f.v[dp] = ld_kv<NT>(reinterpret_cast<const bf16_t*>(v0 + dp * 1024));
+    f.ks = *reinterpret_cast<const uint2*>(ksb + slice * 32 + 8 * lg);
+    f.vs = *reinterpret_cast<const uint2*>(vsb + slice * 32 + 8 * lg);
+}
+ZK_DEV void keep_live(const KV8Frag& f) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { keep_live(f.k[i >> 1][i & 1]); keep_live(f.v[i]); }
+    keep_live(f.ks);
+    keep_live(f.vs);
+}
+
+// four e4m3fn bytes -> four bf16 (exact)
+ZK_DEV uint2 cvt4(uint32_t w) {
+    const bf16x2_t lo = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, false);
+    const bf16x2_t hi = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, true);
+    return make_uint2(__builtin_bit_cast(uint32_t, lo), __builtin_bit_cast(uint32_t, hi));
+}
+ZK_DEV void cvt16(uint4 raw, uint4& a, uint4& b) {
+    const uint2 x = cvt4(raw.x), y = cvt4(raw.y), z = cvt4(raw.z), w = cvt4(raw.w);
+    a = make_uint4(x.x, x.y, y.x, y.y);
+    b = make_uint4(z.x, z.y, w.x, w.y);
+}
+ZK_DEV void scales8(uint2 b, float* s) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        s[j] = __uint_as_float(((b.x >> (8 * j)) & 0xffu) << 23);
+        s[4 + j] = __uint_as_float(((b.y >> (8 * j)) & 0xffu) << 23);
+    }
+}
+// one 32-key step: dequantise in registers, then the bf16 step with the scales on the scores and on p
+ZK_DEV void attn_step8(AttnState& st, const KV8Frag& f, const bf16x8* qf, int key_base, int ctx, float scale, int lg) {
+    KVFrag d;
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int kp = 0; kp < 2; ++kp) cvt16(f.k[h][kp], d.k[h][2 * kp], d.k[h][2 * kp + 1]);
+#pragma unroll
+    for (int dp = 0; dp < 4; ++dp) cvt16(f.v[dp], d.v[2 * dp], d.v[2 * dp + 1]);
+    float sk[8], sv[8];
+    scales8(f.ks, sk);
+    scales8(f.vs, sv);
+    attn_step<true>(st, d, qf, key_base, ctx, scale, lg, sk, sv);
+}
+
+// the new key's bytes and scales (fused form), kept in LDS until the end of the kernel
+struct __attribute__((aligned(16))) Attn8Smem {
+    uint32_t k8[32];     // 128 e4m3fn bytes in dim order
+    uint32_t v8[32];
+    uint32_t sc[2];      // scale byte of the new key (0) and value (1)
+};
+ZK_DEV uint2 put_byte(uint2 v, int e, uint32_t b) {      // byte e (0..7) of the 8 <- b
+    uint64_t x = (uint64_t)v.x | ((uint64_t)v.y << 32);
+    x = (x & ~(0xffull << (8 * e))) | ((uint64_t)b << (8 * e));
+    return make_uint2((uint32_t)x, (uint32_t)(x >> 32));
+}
+// Replace the newest key's bytes and scales in a loaded 32-key slice by the ones kept in LDS (their
+// cache lines are written at the end of the kernel), like patch_kv. Wave-uniform early out.
+ZK_DEV void patch_kv8(KV8Frag& f, const Attn8Smem& s8, int key_base, int pos, int ln, int lg) {
+    if (pos < key_base || pos >= key_base + 32) return;
+    const uint8_t* kn = reinterpret_cast<const uint8_t*>(s8.k8);
+    const uint8_t* vn = reinterpret_cast<const uint8_t*>(s8.v8);
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int key = key_base + 8 * (ln >> 2) + 4 * h + (ln & 3);
+        if (key == pos) {
+#pragma unroll
+            for (int kp = 0; kp < 2; ++kp) {
+                const uint2 a = *reinterpret_cast<const uint2*>(kn + 64 * kp + 8 * lg);
+                const uint2 b = *reinterpret_cast<const uint2*>(kn + 64 * kp + 32 + 8 * lg);
+                f.k[h][kp] = make_uint4(a.x, a.y, b.x, b.y);
+            }
+        }
+    }
+    const int e = pos - key_base - 8 * lg;      // element of this lane's 8-key group
+    if (e >= 0 && e < 8) {
+#pragma unroll
+        for (int dp = 0; dp < 4; ++dp) {
+            const uint2 a = put_byte(make_uint2(f.v[dp].x, f.v[dp].y), e, vn[32 * dp + ln]);
+            const uint2 b = put_byte(make_uint2(f.v[dp].z, f.v[dp].w), e, vn[32 * dp + 16 + ln]);
+            f.v[dp] = make_uint4(a.x, a.y, b.x, b.y);
+        }
+        f.ks = put_byte(f.ks, e, s8.sc[0]);
+        f.vs = put_byte(f.vs, e, s8.sc[1]);
+    }
+}
+
+// qkv_prologue and attn_finish restate attn_decode_wg's slab-reduce / RoPE loop and its wave-merge tail
+// line for line; the bf16 kernel keeps its own inline copies so that its generated code stays what it was.
+// The in_proj epilogue of one workgroup, pairs first, first + 256, ... of [0, (G + 2) * 64): q of heads
+// g*G.. (RoPE) into sm.s_q, then the new key (RoPE) into sm.s_kn and the new value into sm.s_vn. prow: the
+// row's first slab, fc: the position's (cos, sin) row.
+template <bool NEOX>
+ZK_DEV void qkv_prologue(AttnSmem& sm, int first, const float* prow, size_t slab, int gsplit, const float* fc,
+                         int g, int G, int H, int Hkv) {
+    constexpr int HD = 128;
+    uint16_t* q16 = reinterpret_cast<uint16_t*>(&sm.s_q[0][0]);
+    uint16_t* k16 = reinterpret_cast<uint16_t*>(sm.s_kn);
+    auto& s_vn = sm.s_vn;
+    for (int pi = first; pi < (G + 2) * (HD / 2); pi += 256) {
+        const int hp = pi / (HD / 2), j = pi % (HD / 2);      // hp < G: q head g*G+hp; G: k; G+1: v
+        int d0, d1;
+        rope_dims<NEOX>(j, HD, d0, d1);
+        const int cb = hp < G ? (g * G + hp) * HD : (hp == G ? H * HD + g * HD : (H + Hkv) * HD + g * HD);
+        // all slab loads issued together (clamped slab index, select after) -- same
+        // left-to-right fp32 sum as k_qkv_rope
+        // the slab count is dispatched to an exact-size instantiation (B <= 8: 1 slab, c3: 4),
+        // so only real slabs are loaded (one 8-byte load per slab for the interleaved pair)
+        float a, bb;
+        switch (gsplit) {
+            case 1: slab_pair<1, NEOX>(prow + cb, slab, d0, d1, a, bb); break;
+            case 2: slab_pair<2, NEOX>(prow + cb, slab, d0, d1, a, bb); break;
+            case 4: slab_pair<4, NEOX>(prow + cb, slab, d0, d1, a, bb); break;
+            default: slab_pair_n(prow + cb, slab, gsplit, d0, d1, a, bb); break;
+        }
+        const float2 cs = *reinterpret_cast<const float2*>(fc + 2 * j);
+        a = round_bf(a);
+        bb = round_bf(bb);
+        if (hp <= G) {
+            const float o0 = __fsub_rn(__fmul_rn(a, cs.x), __fmul_rn(bb, cs.y));
+            const float o1 = __fadd_rn(__fmul_rn(bb, cs.x), __fmul_rn(a, cs.y));
+            uint16_t* dst = hp < G ? q16 + hp * HD : k16;
+            dst[d0] = f2bf(o0);
+            dst[d1] = f2bf(o1);
+        } else {
+            s_vn[d0] = f2bf(a);
+            s_vn[d1] = f2bf(bb);
+        }
+    }
+}
+
+// The end of a decode-attention workgroup: the 4 waves merge their (m, l, O) through LDS, then nsplit == 1
+// writes the normalised bf16 output, nsplit > 1 the split's partial to `work` and, COMB, the workgroup
+// drawing the launch's last ticket on cnt[row][kv head] merges all partials (k_attn_combine's arithmetic).
+template <bool COMB, class Bar>
+ZK_DEV void attn_finish(AttnSmem& sm, const Bar& bar, const AttnState& st, int split, int nsplit, int g, int r,
+                        int H, int Hkv, float* work, bf16_t* out, uint32_t* cnt) {
+    constexpr int HD = 128;
+    auto& s_m = sm.s_m;
+    auto& s_l = sm.s_l;
+    auto& s_o = sm.s_o;
+    auto& s_last = sm.s_last;
+    const int G = H / Hkv;
+    const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int ln = lane & 15, lg = lane >> 4;
+    // merge the 4 waves
+    if (lg == 0) { s_m[w][ln] = st.m; s_l[w][ln] = st.l; }
+    bar();
+    const float M = fmaxf(fmaxf(s_m[0][ln], s_m[1][ln]), fmaxf(s_m[2][ln], s_m[3][ln]));
+    const float cw = (st.m == -INFINITY) ? 0.f : __expf(st.m - M);
+    if (ln < AT_G) {
+#pragma unroll
+        for (int dt = 0; dt < 8; ++dt)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) s_o[w][ln][dt * 16 + lg * 4 + i] = st.o[dt][i] * cw;
+    }
+    bar();
+    if (nsplit == 1) {
+        // normalised output for the G heads: thread -> (head, 2 channels)
+        for (int i = threadIdx.x; i < G * HD / 2; i += 256) {
+            const int h = i / (HD / 2), d = (i % (HD / 2)) * 2;
+            float Mh = -INFINITY;
+            for (int k = 0; k < 4; ++k) Mh = fmaxf(Mh, s_m[k][h]);
+            float L = 0.f;
+            for (int k = 0; k < 4; ++k) L += (s_m[k][h] == -INFINITY) ? 0.f : s_l[k][h] * __expf(s_m[k][h] - Mh);
+            const float o0 = s_o[0][h][d] + s_o[1][h][d] + s_o[2][h][d] + s_o[3][h][d];
+            const float o1 = s_o[0][h][d + 1] + s_o[1][h][d + 1] + s_o[2][h][d + 1] + s_o[3][h][d + 1];
+            const float inv = 1.0f / L;
+            *reinterpret_cast<uint32_t*>(out + (size_t)r * H * HD + (size_t)(g * G + h) * HD + d) =
+                pack2(o0 * inv, o1 * inv);
+        }
+        return;
+    }
+    float* wp = work + (((size_t)r * Hkv + g) * nsplit + split) * AT_STR;
+    for (int i = threadIdx.x; i < AT_G * HD; i += 256) {
+        const int h = i / HD, d = i % HD;
+        wp[2 * AT_G + i] = s_o[0][h][d] + s_o[1][h][d] + s_o[2][h][d] + s_o[3][h][d];
+    }
+    if (threadIdx.x < AT_G) {
+        const int h = threadIdx.x;
+        float Mh = -INFINITY;
+        for (int k = 0; k < 4; ++k) Mh = fmaxf(Mh, s_m[k][h]);
+        float L = 0.f;
+        for (int k = 0; k < 4; ++k) L += (s_m[k][h] == -INFINITY) ? 0.f : s_l[k][h] * __expf(s_m[k][h] - Mh);
+        wp[h] = Mh;
+        wp[AT_G + h] = L;
+    }
+    if constexpr (COMB) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // every storing wave drains
+        bar();
+        if (threadIdx.x == 0) {
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // keep the fence's wait (ROCm 7.2)
+            const uint32_t old = __hip_atomic_fetch_add(cnt + (size_t)r * Hkv + g, 1u, __ATOMIC_RELAXED,
+                                                        __HIP_MEMORY_SCOPE_AGENT);
+            s_last = ((old + 1) % (uint32_t)nsplit) == 0;
+        }
+        bar();
+        if (!s_last) return;
+        if (threadIdx.x == 0) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+        bar();
+        const float* base = work + ((size_t)r * Hkv + g) * nsplit * AT_STR;
+        for (int i = threadIdx.x; i < G * HD / 2; i += 256) {       // k_attn_combine's arithmetic
+            const int j = i / (HD / 2), d = (i % (HD / 2)) * 2;
+            float M = -INFINITY;
+            for (int sp = 0; sp < nsplit; ++sp) M = fmaxf(M, base[sp * AT_STR + j]);
+            float L = 0.f, o0 = 0.f, o1 = 0.f;
+            for (int sp = 0; sp < nsplit; ++sp) {
+                const float* p = base + sp * AT_STR;
+                const float c = (p[j] == -INFINITY) ? 0.f : __expf(p[j] - M);
+                L += p[AT_G + j] * c;
+                o0 += p[2 * AT_G + j * HD + d] * c;
+                o1 += p[2 * AT_G + j * HD + d + 1] * c;
+            }
+            const float inv = 1.0f / L;
+            *reinterpret_cast<uint32_t*>(out + (size_t)r * H * HD + (size_t)(g * G + j) * HD + d) =
+                pack2(o0 * inv, o1 * inv);
+        }
+    }
+}
+
+// grid (nsplit, Hkv, R), 256 threads. FUSED: part / gsplit / freqs are the in_proj slabs and the RoPE table
+// (interleaved pairs) and the workgroup of the last split stores the new key's bytes and scales at the end;
+// otherwise q holds the query rows. COMB (FUSED, nsplit > 1): in-launch combine on cnt.
+template <bool FUSED, bool KVNT, bool COMB>
+__global__ __launch_bounds__(256, 2) void k_attn_decode_f8(const bf16_t* q, uint8_t* k8, uint8_t* v8, uint8_t* ksc,
+                                                           uint8_t* vsc, int R, int H, int Hkv, int Smax, int ctx0,
+                                                           const int32_t* ctx_dev, float* work, float scale,
+                                                           bf16_t* out, const int32_t* skip, const float* part,
+                                                           int gsplit, const float* freqs, uint32_t* cnt) {
+    constexpr int HD = 128;
+    __shared__ AttnSmem sm;
+    __shared__ Attn8Smem s8;
+    const int sk = ld_word(skip);
+    const int cwr = ld_word(ctx_dev);
+    const int split = blockIdx.x, nsplit = gridDim.x, g = blockIdx.y, r = blockIdx.z;
+    const auto bar = [] { __syncthreads(); };
+    // (the context is clamped to the cache: a skipped launch after the last step may see ctx = Smax + 1)
+    const int ctx = max(1, min(ctx0 + uni(cwr), Smax));
+    const int nkb = (ctx + AT_KB - 1) / AT_KB;
+    const int kb0 = (int)((long)split * nkb / nsplit), kb1 = (int)((long)(split + 1) * nkb / nsplit);
+    const int G = H / Hkv;
+    const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int ln = lane & 15, lg = lane >> 4;
+    const size_t blk = (size_t)r * Hkv + g;
+    uint8_t* kb = k8 + blk * Smax * HD;
+    uint8_t* vb = v8 + blk * Smax * HD;
+    uint8_t* ksb = ksc + blk * Smax;
+    uint8_t* vsb = vsc + blk * Smax;
+    // this wave's slice of key block b, clamped into the cache whatever b is (see the in-bounds note above)
+    const int nsl = Smax >> 5;
+    const auto slice_of = [&](int b) { return max(0, min(b * 4 + w, nsl - 1)); };
+    // as attn_decode_wg: the wave multiplies only the blocks whose slice holds a visible key
+    const int vis = ctx - 32 * w;
+    const int kbw = vis <= 0 ? kb0 : max(kb0, min(kb1, (vis + AT_KB - 1) / AT_KB));
+    const int last = kbw - 1;
+    const int pos = ctx - 1;
+    KV8Frag fa, fb;
+    // the first two key blocks are requested before the skip word is tested and stream during the prologue
+    load_kv8<KVNT>(fa, kb, vb, ksb, vsb, slice_of(kb0), lane, lg);
+    load_kv8<KVNT>(fb, kb, vb, ksb, vsb, slice_of(min(kb0 + 1, max(last, kb0))), lane, lg);
+    if (uni(sk) != 0) {      // skip: nothing is written
+        keep_live(fa);
+        keep_live(fb);
+        return;
+    }
+    bf16x8 qf[4];
+    if constexpr (FUSED) {
+        const int N = (H + 2 * Hkv) * HD;
+        qkv_prologue<false>(sm, threadIdx.x, part + (size_t)r * N, (size_t)R * N, gsplit, freqs + (size_t)pos * HD, g, G,
+                            H, Hkv);
+        bar();      // q, new k, new v (bf16) in LDS
+        if (w < 2) {      // wave 0 quantises the new key, wave 1 the new value: one amax over the 128 dims each
+            const uint32_t pr = w == 0 ? sm.s_kn[lane] : reinterpret_cast<const uint32_t*>(sm.s_vn)[lane];
+            const float a = __uint_as_float(pr << 16), b = __uint_as_float(pr & 0xffff0000u);
+            const int e = kv_scale_exp(wave_max(fmaxf(fabsf(a), fabsf(b))));
+            uint16_t* dst = reinterpret_cast<uint16_t*>(w == 0 ? s8.k8 : s8.v8);
+            dst[lane] = (uint16_t)quant2(a, b, kv_pow2(-e));
+            if (lane == 0) s8.sc[w] = (uint32_t)(e + 127);
+        }
+        bar();
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) {
+            uint4 v = make_uint4(0, 0, 0, 0);
+            if (ln < G) v = *reinterpret_cast<const uint4*>(&sm.s_q[ln][ks * 16 + lg * 4]);
+            qf[ks] = as_frag(v);
+        }
+    } else {
+        const bf16_t* qr = q + (size_t)r * H * HD + (size_t)(g * G + ln) * HD;
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) {
+            uint4 v = make_uint4(0, 0, 0, 0);
+            if (ln < G) v = *reinterpret_cast<const uint4*>(qr + ks * 32 + lg * 8);
+            qf[ks] = as_frag(v);
+        }
+    }
+    AttnState st;
+    st.m = -INFINITY;
+    st.l = 0.f;
+#pragma unroll
+    for (int dt = 0; dt < 8; ++dt) st.o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int it = kb0; it < kbw; it += 2) {
+        if (it != kb0 && it + 1 < kbw) load_kv8<KVNT>(fb, kb, vb, ksb, vsb, slice_of(it + 1), lane, lg);
+        if (FUSED) patch_kv8(fa, s8, it * AT_KB + 32 * w, pos, ln, lg);
+        attn_step8(st, fa, qf, it * AT_KB + 32 * w, ctx, scale, lg);
+        if (it + 2 < kbw) load_kv8<KVNT>(fa, kb, vb, ksb, vsb, slice_of(it + 2), lane, lg);
+        if (it + 1 < kbw) {
+            if (FUSED) patch_kv8(fb, s8, (it + 1) * AT_KB + 32 * w, pos, ln, lg);
+            attn_step8(st, fb, qf, (it + 1) * AT_KB + 32 * w, ctx, scale, lg);
+        }
+    }
+    if (FUSED && split == nsplit - 1) {      // the split owning the newest key stores it (cache for later steps)
+        const int t = threadIdx.x;
+        if (t < 16) *reinterpret_cast<uint2*>(kb + k8_off(pos, t)) = reinterpret_cast<const uint2*>(s8.k8)[t];
+        else if (t < 16 + HD) vb[v8_off(pos, t - 16)] = reinterpret_cast<const uint8_t*>(s8.v8)[t - 16];
+        else if (t == 16 + HD) ksb[pos] = (uint8_t)s8.sc[0];
+        else if (t == 17 + HD) vsb[pos] = (uint8_t)s8.sc[1];
+    }
+    attn_finish<COMB>(sm, bar, st, split, nsplit, g, r, H, Hkv, work, out, cnt);
+}
+
+// Keys [0, S) of a bf16 fragment-ordered K / V^T cache pair of Ssrc keys per (row, kv head) (a layer's
+// prefill scratch) -> the FP8 cache of Smax keys plus scales. grid (ceil(S / 32), Hkv, R), 256 threads:
+// thread t takes 16 dims of key t >> 3 of the slice; the 8 threads of a key reduce its amax.
+__global__ __launch_bounds__(256) void k_kv_quantize_e4m3(const bf16_t* ksrc, const bf16_t* vsrc, int Hkv, int S,
+                                                          int Ssrc, uint8_t* k8, uint8_t* v8, uint8_t* ksc,
+                                                          uint8_t* vsc, int Smax) {
+    const int key = blockIdx.x * 32 + (threadIdx.x >> 3), j = threadIdx.x & 7;      // key < Ssrc (Ssrc % 32 == 0)
+    const size_t blk = (size_t)blockIdx.z * Hkv + blockIdx.y;
+    const bf16_t* ks = ksrc + blk * Ssrc * 128;
+    const bf16_t* vs = vsrc + blk * Ssrc * 128;
+    float fk[16], fv[16];
+    unpack8(*reinterpret_cast<const uint4*>(ks + k_off(key, 2 * j)), fk);
+    unpack8(*reinterpret_cast<const uint4*>(ks + k_off(key, 2 * j + 1)), fk + 8);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) fv[i] = bf2f(vs[v_off(key, 16 * j + i)]);
+    float ak = 0.f, av = 0.f;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) { ak = fmaxf(ak, fabsf(fk[i])); av = fmaxf(av, fabsf(fv[i])); }
+#pragma unroll
+    for (int o = 1; o < 8; o <<= 1) { ak = fmaxf(ak, __shfl_xor(ak, o, 64)); av = fmaxf(av, __shfl_xor(av, o, 64)); }
+    if (key >= S) return;      // destination keys >= S stay untouched
+    const int ek = kv_scale_exp(ak), ev = kv_scale_exp(av);
+    const float ik = kv_pow2(-ek), iv = kv_pow2(-ev);
+    uint8_t* kd = k8 + blk * Smax * 128;
+    uint8_t* vd = v8 + blk * Smax * 128;
+    *reinterpret_cast<uint2*>(kd + k8_off(key, 2 * j)) = make_uint2(quant4(fk, ik), quant4(fk + 4, ik));
+    *reinterpret_cast<uint2*>(kd + k8_off(key, 2 * j + 1)) = make_uint2(quant4(fk + 8, ik), quant4(fk + 12, ik));
+#pragma unroll
+    for (int i = 0; i < 16; i += 4) {
+        const uint32_t wv = quant4(fv + i, iv);
+#pragma unroll
+        for (int b = 0; b < 4; ++b) vd[v8_off(key, 16 * j + i + b)] = (uint8_t)(wv >> (8 * b));
+    }
+    if (j == 0) {
+        ksc[blk * Smax + key] = (uint8_t)(ek + 127);
+        vsc[blk * Smax + key] = (uint8_t)(ev + 127);
+    }
+}
+
+}  // namespace
+
+// ------------------------------------------------------------------ entries
+#define ZK_F8_REQUIRE(name)                                                                                   \
+    ZK_REQUIRE(hd == 128, name ": head_dim %d unsupported (128 only)", hd);                                   \
+    ZK_REQUIRE(H % Hkv == 0 && H / Hkv <= AT_G, name ": GQA group %d > %d", H / Hkv, AT_G);                   \
+    ZK_REQUIRE(Smax > 0 && Smax % AT_KB == 0, name ": Smax=%d must be a multiple of %d", Smax, AT_KB);        \
+    ZK_REQUIRE(nsplit >= 1 && nsplit <= Smax / AT_KB, name ": nsplit=%d out of [1, %d]", nsplit, Smax / AT_KB); \
+    ZK_REQUIRE(nsplit == 1 || work != nullptr, name ": nsplit > 1 needs the work buffer");                    \
+    ZK_REQUIRE(k8 != nullptr && v8 != nullptr && k_scale != nullptr && v_scale != nullptr && out != nullptr,  \
+               name ": null cache, scale or output buffer")
+
+// non-temporal KV loads by the KV_NT_BYTES rule on the FP8 byte count (K8 + V8)
+static bool f8_kvnt(int R, int Hkv, int Smax, int hd) { return (double)R * Hkv * Smax * hd * 2 >= KV_NT_BYTES; }
+
+extern "C" int zk_kv_quantize_e4m3(const void* k_src, const void* vt_src, int R, int Hkv, int hd, int S, int Smax_src,
+                                   void* k8, void* v8, void* k_scale, void* v_scale, int Smax, void* stream) {
+    ZK_REQUIRE(hd == 128, "zk_kv_quantize_e4m3: head_dim %d unsupported (128 only)", hd);
+    ZK_REQUIRE(Smax > 0 && Smax % AT_KB == 0, "zk_kv_quantize_e4m3: Smax=%d must be a multiple of %d", Smax, AT_KB);
+    ZK_REQUIRE(Smax_src > 0 && Smax_src % 32 == 0, "zk_kv_quantize_e4m3: Smax_src=%d must be a multiple of 32",
+               Smax_src);
+    ZK_REQUIRE(S >= 0 && S <= Smax && S <= Smax_src, "zk_kv_quantize_e4m3: S=%d beyond Smax=%d / Smax_src=%d", S, Smax,
+               Smax_src);
+    ZK_REQUIRE(k_src != nullptr && vt_src != nullptr && k8 != nullptr && v8 != nullptr && k_scale != nullptr &&
+                   v_scale != nullptr,
+               "zk_kv_quantize_e4m3: null buffer");
+    if (R * Hkv * S == 0) return 0;
+    hipLaunchKernelGGL(k_kv_quantize_e4m3, dim3((S + 31) / 32, Hkv, R), dim3(256), 0, (hipStream_t)stream,
+                       (const bf16_t*)k_src, (const bf16_t*)vt_src, Hkv, S, Smax_src, (uint8_t*)k8, (uint8_t*)v8,
+                       (uint8_t*)k_scale, (uint8_t*)v_scale, Smax);
+    ZK_CHECK_LAUNCH("zk_kv_quantize_e4m3");
+    return 0;
+}
+
+extern "C" int zk_attn_decode_f8(const void* q, const void* k8, const void* v8, const void* k_scale,
+                                 const void* v_scale, int R, int H, int Hkv, int hd, int Smax, int ctx0,
+                                 const int32_t* ctx_dev, float* work, int nsplit, void* out, const int32_t* skip,
+                                 void* stream) {
+    ZK_F8_REQUIRE("zk_attn_decode_f8");
+    ZK_REQUIRE(q != nullptr, "zk_attn_decode_f8: null q");
+    const float scale = 1.0f / sqrtf((float)hd);
+    auto kern = f8_kvnt(R, Hkv, Smax, hd) ? k_attn_decode_f8<false, true, false> : k_attn_decode_f8<false, false, false>;
+    hipLaunchKernelGGL(kern, dim3(nsplit, Hkv, R), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)q, (uint8_t*)k8,
+                       (uint8_t*)v8, (uint8_t*)k_scale, (uint8_t*)v_scale, R, H, Hkv, Smax, ctx0, ctx_dev, work, scale,
+                       (bf16_t*)out, skip, nullptr, 0, nullptr, nullptr);
+    ZK_CHECK_LAUNCH("zk_attn_decode_f8");
+    if (nsplit > 1) {
+        hipLaunchKernelGGL(k_attn_combine, dim3(H, R), dim3(64), 0, (hipStream_t)stream, work, H, Hkv, nsplit,
+                           (bf16_t*)out, skip);
+        ZK_CHECK_LAUNCH("zk_attn_combine");
+    }
+    return 0;
+}
+
+extern "C" int zk_attn_decode_qkv_f8(const float* part, int gemm_nsplit, const float* freqs, void* k8, void* v8,
+                                     void* k_scale, void* v_scale, int R, int H, int Hkv, int hd, int Smax, int ctx0,
+                                     const int32_t* ctx_dev, float* work, int nsplit, uint32_t* counters, void* out,
+                                     const int32_t* skip, void* stream) {
+    ZK_F8_REQUIRE("zk_attn_decode_qkv_f8");
+    ZK_REQUIRE(part != nullptr && freqs != nullptr && gemm_nsplit >= 1 && gemm_nsplit <= AT_MAXGS,
+               "zk_attn_decode_qkv_f8: bad arguments (gemm_nsplit=%d, max %d)", gemm_nsplit, AT_MAXGS);
+    const float scale = 1.0f / sqrtf((float)hd);
+    const bool nt = f8_kvnt(R, Hkv, Smax, hd), comb = nsplit > 1 && counters != nullptr;
+    auto kern = comb ? (nt ? k_attn_decode_f8<true, true, true> : k_attn_decode_f8<true, false, true>)
+                     : (nt ? k_attn_decode_f8<true, true, false> : k_attn_decode_f8<true, false, false>);
+    hipLaunchKernelGGL(kern, dim3(nsplit, Hkv, R), dim3(256), 0, (hipStream_t)stream, nullptr, (uint8_t*)k8,
+                       (uint8_t*)v8, (uint8_t*)k_scale, (uint8_t*)v_scale, R, H, Hkv, Smax, ctx0, ctx_dev, work, scale,
+                       (bf16_t*)out, skip, part, gemm_nsplit, freqs, counters);
+    ZK_CHECK_LAUNCH("zk_attn_decode_qkv_f8");
+    if (nsplit > 1 && !comb) {
+        hipLaunchKernelGGL(k_attn_combine, dim3(H, R), dim3(64), 0, (hipStream_t)stream, work, H, Hkv, nsplit,
+                           (bf16_t*)out, skip);
+        ZK_CHECK_LAUNCH("zk_attn_combine");
+    }
+    return 0;
+}
+#undef ZK_F8_REQUIRE

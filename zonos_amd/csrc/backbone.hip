@@ -793,3 +793,6 @@ extern "C" int zk_attn_prefill(const void* q, const void* k_cache, const void* v
     ZK_CHECK_LAUNCH("zk_attn_prefill");
     return 0;
 }
+
+// FP8 KV cache: decode attention and the post-prefill quantiser (zk_*_f8, zk_kv_quantize_e4m3)
+#include "attn_f8.h"

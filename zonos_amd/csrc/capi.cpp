@@ -11,6 +11,11 @@
 #include "../../include/zonos_hip.h"
 #include "warm.h"
 
+// The FP8 KV-cache entries live with their kernels (backbone.hip). Weak here, so that this file alone still
+// links in a host-only build that provides just the entries it drives; fp8_ok() refuses kv_fp8 without them.
+#pragma weak zk_attn_decode_qkv_f8
+#pragma weak zk_kv_quantize_e4m3
+
 static thread_local char g_err[1024] = "";
 
 extern "C" void zk_set_error(const char* fmt, ...) {
@@ -26,7 +31,7 @@ extern "C" int zk_version(void) { return 1; }
 
 // sizeof / offsetof of the by-value ABI structs, so a binding (ctypes here) can verify its
 // layout without a GPU: which = 0 zk_sampling_params, 1 zk_gen_state, 4 ZkCondSeg, 5 ZkCondPlan,
-// 6 zk_step_layer, 7 zk_step_desc, 8 zk_dac_desc; 12-21 sizes / field offsets (see the cases).
+// 6 zk_step_layer, 7 zk_step_desc, 8 zk_dac_desc; 12-25 sizes / field offsets (see the cases).
 extern "C" long zk_abi_size(int which) {
     switch (which) {
         case 0: return (long)sizeof(zk_sampling_params);
@@ -47,6 +52,9 @@ extern "C" long zk_abi_size(int which) {
         case 20: return (long)offsetof(zk_hybrid_desc, st);
         case 21: return (long)offsetof(zk_hybrid_desc, eps);
         case 22: return (long)offsetof(zk_gen_state, noise_offset);
+        case 23: return (long)offsetof(zk_step_desc, kv_fp8);
+        case 24: return (long)offsetof(zk_step_desc, pre_k);
+        case 25: return (long)offsetof(zk_step_layer, k_scale);
         default: return -1;
     }
 }
@@ -205,10 +213,21 @@ int transformer_layers(const zk_step_desc* d, int R, int S, bool prefill, void* 
     for (int i = 0; i < d->n_layer; ++i) {
         const zk_step_layer& L = d->layers[i];
         ZK_STEP(zk_gemm_bf16(d->xn, D, L.wqkv, M, Nqkv, D, sq, 0, d->part, nullptr, skip, stream));
-        if (prefill) {
+        if (prefill && d->kv_fp8) {
+            // exact prefill on the bf16 scratch pair (one layer live at a time), then this layer's FP8 cache
+            ZK_STEP(zk_qkv_rope(d->part, 1, R, S, H, Hk, hd, d->freqs, 0, nullptr, q, d->pre_k, d->pre_vt, d->pre_smax,
+                                nullptr, 0, nullptr, stream));
+            ZK_STEP(zk_attn_prefill(q, d->pre_k, d->pre_vt, R, S, H, Hk, hd, d->pre_smax, d->y, stream));
+            ZK_STEP(zk_kv_quantize_e4m3(d->pre_k, d->pre_vt, R, Hk, hd, S, d->pre_smax, L.k_cache, L.vt_cache, L.k_scale,
+                                        L.v_scale, d->smax, stream));
+        } else if (prefill) {
             ZK_STEP(zk_qkv_rope(d->part, 1, R, S, H, Hk, hd, d->freqs, 0, nullptr, q, L.k_cache, L.vt_cache, d->smax,
                                 nullptr, d->rope_neox, nullptr, stream));
             ZK_STEP(zk_attn_prefill(q, L.k_cache, L.vt_cache, R, S, H, Hk, hd, d->smax, d->y, stream));
+        } else if (d->kv_fp8) {
+            ZK_STEP(zk_attn_decode_qkv_f8(d->part, sq, d->freqs, L.k_cache, L.vt_cache, L.k_scale, L.v_scale, R, H, Hk,
+                                          hd, d->smax, 1, pos, d->attn_work, d->attn_splits, d->attn_cnt, d->y, skip,
+                                          stream));
         } else {
             ZK_STEP(zk_attn_decode_qkv_sc(d->part, sq, d->freqs, L.k_cache, L.vt_cache, R, H, Hk, hd, d->smax, 1, pos,
                                           d->attn_work, d->attn_splits, d->attn_cnt, d->y, d->rope_neox, skip,
@@ -231,6 +250,36 @@ int transformer_layers(const zk_step_desc* d, int R, int S, bool prefill, void* 
 }
 
 bool step_ok(const zk_step_desc* d) { return d != nullptr && d->layers != nullptr && d->n_layer > 0 && d->B > 0; }
+
+// kv_fp8 descriptors are checked whole before the first launch (prefill: also the bf16 scratch pair)
+int fp8_ok(const char* who, const zk_step_desc* d, bool prefill, int S) {
+    if (!d->kv_fp8) return 0;
+    if (&zk_attn_decode_qkv_f8 == nullptr || &zk_kv_quantize_e4m3 == nullptr) {
+        zk_set_error("%s: this build has no FP8 KV-cache kernels", who);
+        return -1;
+    }
+    if (d->small) {
+        zk_set_error("%s: kv_fp8 = 1 runs the seven-launch sequence only (small must be 0)", who);
+        return -1;
+    }
+    if (d->rope_neox || d->head_dim != 128 || d->smax % 128 != 0) {
+        zk_set_error("%s: kv_fp8 needs interleaved RoPE, head_dim 128 and smax %% 128 == 0", who);
+        return -1;
+    }
+    for (int i = 0; i < d->n_layer; ++i) {
+        const zk_step_layer& L = d->layers[i];
+        if (L.k_cache == nullptr || L.vt_cache == nullptr || L.k_scale == nullptr || L.v_scale == nullptr) {
+            zk_set_error("%s: kv_fp8 layer %d lacks its cache or scale pointers", who, i);
+            return -1;
+        }
+    }
+    if (prefill && (d->pre_k == nullptr || d->pre_vt == nullptr || d->pre_smax < S || d->pre_smax % 32 != 0)) {
+        zk_set_error("%s: kv_fp8 needs the bf16 prefill scratch pair (pre_k, pre_vt, pre_smax=%d >= S=%d, %% 32 == 0)",
+                     who, d->pre_smax, S);
+        return -1;
+    }
+    return 0;
+}
 }  // namespace
 
 extern "C" int zk_decode_step(const zk_step_desc* d, void* stream) {
@@ -238,6 +287,7 @@ extern "C" int zk_decode_step(const zk_step_desc* d, void* stream) {
         zk_set_error("zk_decode_step: bad descriptor");
         return -1;
     }
+    ZK_STEP(fp8_ok("zk_decode_step", d, false, 0));
     const int K = d->st.K, V = d->st.V, B = d->B, R = 2 * B;
     const int D = d->d_model, H = d->n_heads, Hk = d->n_kv, hd = d->head_dim, Fd = d->d_ff;
     const int Nqkv = (H + 2 * Hk) * hd;
@@ -291,6 +341,7 @@ extern "C" int zk_decode_step(const zk_step_desc* d, void* stream) {
 }
 
 extern "C" int zk_prefill(const zk_step_desc* d, const void* cond, int Lc, int P, void* q, void* stream) {
+    if (step_ok(d)) ZK_STEP(fp8_ok("zk_prefill", d, true, Lc + P + 1));
     ZK_STEP(prefill_prologue("zk_prefill", step_ok(d), d, cond, Lc, P, q, stream));
     const int R = 2 * d->B, S = Lc + P + 1;
     ZK_STEP(zk_layernorm(d->x, d->layers[0].ln1_w, d->layers[0].ln1_b, d->eps, R * S, d->d_model, d->xn, stream));

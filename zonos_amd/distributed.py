@@ -120,7 +120,7 @@ def generate_sharded(model, prefix_conditioning: torch.Tensor, audio_prefix_code
       the global list (utterance order) on every rank, else the rank's own list;
       ``return_local`` returns (the rank's own list on its device, the gathered list).
     ``model`` is a ``zonos_amd.model.Zonos`` or an engine (``HipDecoder`` / ``HybridDecoder``);
-    extra keywords go to its ``generate``. Without an initialised process group this is
+    extra keywords (``kv_dtype="fp8"`` among them) go to its ``generate``. Without an initialised process group this is
     ``model.generate`` on the whole batch."""
     world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
     rank = dist.get_rank(group) if world > 1 else 0

@@ -13,7 +13,9 @@ Design (MI355X-first):
   * Weights are bf16 in HBM in the engine's layouts: 9 embedding tables stacked
     [9][1026][D], the 9 heads stacked [9*1026][D], fc1 rows interleaved for the fused
     SwiGLU epilogue, GEMM weights fragment-packed (zk_pack_weights). The KV cache stores
-    per (row, kv head) 32-key slices in MFMA-fragment order (zonos_amd.kvlayout).
+    per (row, kv head) 32-key slices in MFMA-fragment order (zonos_amd.kvlayout), in bf16 or,
+    opt-in (generate(kv_dtype="fp8") / ZONOS_KV_DTYPE=fp8), as e4m3fn bytes with one power-of-two
+    scale per key: half the KV memory and half the bytes the decode attention streams.
   * torch is plumbing only: it allocates device memory and provides the stream.
 """
 from __future__ import annotations
@@ -21,6 +23,7 @@ from __future__ import annotations
 import ctypes as C
 import logging
 import math
+import os
 from dataclasses import dataclass
 
 import torch
@@ -30,6 +33,17 @@ from . import sampling as zsampling
 from ._lib import GenState, SamplingParams, call, ptr
 
 EOS, MASK, UNKNOWN = 1024, 1025, -1
+KV_DTYPES = ("bf16", "fp8")
+
+
+def resolve_kv_dtype(kv_dtype: str | None) -> str:
+    """generate()'s ``kv_dtype``: None reads the environment variable ZONOS_KV_DTYPE (default bf16)."""
+    if kv_dtype is None:
+        kv_dtype = os.environ.get("ZONOS_KV_DTYPE") or "bf16"
+    if kv_dtype not in KV_DTYPES:
+        raise ValueError(f"kv_dtype must be one of {KV_DTYPES}, not {kv_dtype!r}")
+    return kv_dtype
+
 N_CB = 9
 VOCAB = 1026
 ATTN_CHUNK = 256
@@ -247,10 +261,17 @@ class HipBackbone:
                  stream)
 
     def _kv(self, ws, layer):
+        if ws.get("kv_fp8"):             # a bf16 kernel must never be pointed at the (half as large) byte caches
+            raise ValueError("this workspace holds the FP8 KV cache (bytes + scales, _kv8): "
+                             "the bf16 attention entries cannot read it")
         if "kv_layers" in ws:            # caches handed out per layer (backbone plugin)
             kv = ws["kv_layers"][layer]
             return kv[0], kv[1]
         return ws["kv"][layer, 0], ws["kv"][layer, 1]
+
+    def _kv8(self, ws, layer):
+        """FP8 cache of a layer: K8 and V8 bytes, K and V scale bytes (zonos_amd.kvlayout)."""
+        return ws["kv"][layer, 0], ws["kv"][layer, 1], ws["kv_scale"][layer, 0], ws["kv_scale"][layer, 1]
 
     # ------------------------------------------------------------------ transformer passes
     def _layers(self, ws, M: int, R: int, S: int, prefill: bool, stream, skip):
@@ -263,9 +284,22 @@ class HipBackbone:
         scal = ws["scal"]
         pos_dev = None if prefill else ptr(scal[1:2])
         for i, L in enumerate(self.layers):
-            kc, vt = self._kv(ws, i)
+            fp8 = bool(ws.get("kv_fp8"))
+            kc, vt, ksc, vsc = self._kv8(ws, i) if fp8 else (*self._kv(ws, i), None, None)
             call("zk_gemm_bf16", ptr(xn), D, ptr(L["wqkv"]), M, Nqkv, D, sp["qkv"], 0, ptr(part), None, skip, stream)
-            if prefill:
+            if prefill and fp8:
+                # exact prefill on the reusable bf16 scratch pair, then this layer's FP8 cache
+                pk, pv = ws["pre_kv"][0], ws["pre_kv"][1]
+                call("zk_qkv_rope", ptr(part), sp["qkv"], R, S, H, Hk, hd, ptr(self.freqs), 0, pos_dev, ptr(q),
+                     ptr(pk), ptr(pv), ws["pre_smax"], None, 0, skip, stream)
+                call("zk_attn_prefill", ptr(q), ptr(pk), ptr(pv), R, S, H, Hk, hd, ws["pre_smax"], ptr(y), stream)
+                call("zk_kv_quantize_e4m3", ptr(pk), ptr(pv), R, Hk, hd, S, ws["pre_smax"], ptr(kc), ptr(vt), ptr(ksc),
+                     ptr(vsc), ws["smax"], stream)
+            elif fp8:
+                call("zk_attn_decode_qkv_f8", ptr(part), sp["qkv"], ptr(self.freqs), ptr(kc), ptr(vt), ptr(ksc),
+                     ptr(vsc), R, H, Hk, hd, ws["smax"], 1, ptr(scal[1:2]), ptr(ws["attn_work"]), ws["attn_splits"],
+                     ptr(ws["attn_cnt"]), ptr(y), skip, stream)
+            elif prefill:
                 call("zk_qkv_rope", ptr(part), sp["qkv"], R, S, H, Hk, hd, ptr(self.freqs), 0, pos_dev, ptr(q),
                      ptr(kc), ptr(vt), ws["smax"], None, self.rope_neox, skip, stream)
                 call("zk_attn_prefill", ptr(q), ptr(kc), ptr(vt), R, S, H, Hk, hd, ws["smax"], ptr(y), stream)
@@ -303,6 +337,8 @@ class HipDecoder(HipBackbone):
     # layer 0's norm is fused into the embedding kernel (decode) / a zk_layernorm (prefill); False:
     # the subclass runs it as _prenorm (the hybrid backbone's RMS-norm / fp32-residual variants)
     embed_norm = True
+    kv_fp8_supported = True         # generate(kv_dtype="fp8"): the transformer backbone only
+    _fp8 = False                    # the running generate() uses the FP8 KV cache
 
     def __init__(self, cfg: EngineConfig, weights: dict, device="cuda"):
         super().__init__(cfg, weights, device)
@@ -331,8 +367,13 @@ class HipDecoder(HipBackbone):
     def _new_state(self, R: int, smax: int) -> dict:
         """What a generate() call starts from zeroed: the KV caches and the in-launch split-combine tickets."""
         c, dev = self.cfg, self.device
+        cnt = torch.zeros(R * c.n_kv, dtype=torch.int32, device=dev)
+        if self._fp8:      # e4m3fn bytes + one scale byte per (row, kv head, key) for K and for V (kvlayout)
+            return dict(kv=torch.zeros(c.n_layer, 2, R * c.n_kv * smax * c.head_dim, dtype=torch.uint8, device=dev),
+                        kv_scale=torch.zeros(c.n_layer, 2, R * c.n_kv * smax, dtype=torch.uint8, device=dev),
+                        attn_cnt=cnt)
         return dict(kv=torch.zeros(c.n_layer, 2, R * c.n_kv * smax * c.head_dim, dtype=torch.bfloat16, device=dev),
-                    attn_cnt=torch.zeros(R * c.n_kv, dtype=torch.int32, device=dev))
+                    attn_cnt=cnt)
 
     def _alloc(self, B: int, Lc: int, P: int, max_new: int):
         R = 2 * B
@@ -341,7 +382,7 @@ class HipDecoder(HipBackbone):
         seq_len = Lc + T + N_CB
         smax = -(-seq_len // ATTN_CHUNK) * ATTN_CHUNK
         S_pre = Lc + P + 1
-        key = (B, Lc, P, max_new)
+        key = (B, Lc, P, max_new, "fp8" if self._fp8 else "bf16")
         if self._ws is not None and self._ws["key"] == key:
             ws = self._ws
             for k in ws["state_keys"]:
@@ -356,6 +397,14 @@ class HipDecoder(HipBackbone):
                   attn_merge=attn_merge, state_keys=tuple(state), graph=None, **state,
                   **activation_buffers(self.cfg, self.device, R * S_pre, R, smax, splits, max(attn_splits, attn_merge)),
                   **generation_state(self.device, B, Ld))
+        if self._fp8:
+            # the bf16 K / V^T pair the exact prefill of one layer runs on (zeroed once: the prefill attention
+            # multiplies the masked tail of its last 32-key slice by p = 0)
+            c = self.cfg
+            ws["kv_fp8"] = True
+            ws["pre_smax"] = -(-S_pre // 128) * 128
+            ws["pre_kv"] = torch.zeros(2, R * c.n_kv * ws["pre_smax"] * c.head_dim, dtype=torch.bfloat16,
+                                       device=self.device)
         self._ws = ws
         return ws
 
@@ -393,17 +442,20 @@ class HipDecoder(HipBackbone):
         if "step_layers" not in ws:
             arr = (_lib.StepLayer * c.n_layer)()
             for i, L in enumerate(self.layers):
-                kc, vt = self._kv(ws, i)
+                kc, vt, ksc, vsc = self._kv8(ws, i) if ws.get("kv_fp8") else (*self._kv(ws, i), None, None)
                 arr[i] = _lib.StepLayer(ptr(L["ln1_w"]), ptr(L["ln1_b"]), ptr(L["wqkv"]), ptr(L["wo"]),
-                                        ptr(L["ln2_w"]), ptr(L["ln2_b"]), ptr(L["fc1"]), ptr(L["fc2"]), ptr(kc), ptr(vt))
+                                        ptr(L["ln2_w"]), ptr(L["ln2_b"]), ptr(L["fc1"]), ptr(L["fc2"]), ptr(kc), ptr(vt),
+                                        ptr(ksc), ptr(vsc))
             ws["step_layers"] = arr
         sps = ws["splits"]
         return _lib.StepDesc(B, c.n_layer, c.d_model, c.n_heads, c.n_kv, c.head_dim, c.d_ff, ws["smax"],
                              sps["qkv"], sps["o"], sps["fc2"], sps["heads"], ws["attn_splits"],
                              ws.get("attn_merge", 0), self.rope_neox, int(self._small(2 * B)), c.eps,
-                             C.cast(ws["step_layers"], C.c_void_p), ptr(self.emb), ptr(self.heads), ptr(self.lnf_w),
+                             int(bool(ws.get("kv_fp8"))), C.cast(ws["step_layers"], C.c_void_p), ptr(self.emb), ptr(self.heads), ptr(self.lnf_w),
                              ptr(self.lnf_b), ptr(self.freqs), ptr(ws["x"]), ptr(ws["xn"]), ptr(ws["y"]), ptr(ws["h"]),
-                             ptr(ws["part"]), ptr(ws["attn_work"]), ptr(ws["attn_cnt"]), ptr(ws["dbg"]), st, sp)
+                             ptr(ws["part"]), ptr(ws["attn_work"]), ptr(ws["attn_cnt"]), ptr(ws["dbg"]), st, sp,
+                             ptr(ws["pre_kv"][0]) if "pre_kv" in ws else None,
+                             ptr(ws["pre_kv"][1]) if "pre_kv" in ws else None, ws.get("pre_smax", 0))
 
     def _c_decode(self, ws, B, st, sp, stream):
         call("zk_decode_step", C.byref(self._step_desc(ws, B, st, sp)), stream)
@@ -441,7 +493,8 @@ class HipDecoder(HipBackbone):
         call("zk_eos_step", C.byref(st), 0, 0, stream)
 
     def _small(self, R: int) -> bool:
-        return self.small_batch_path and R <= 16 and self.cfg.d_model == 2048
+        # (the FP8 KV cache runs the seven-launch sequence at any batch size)
+        return self.small_batch_path and R <= 16 and self.cfg.d_model == 2048 and not self._fp8
 
     # ------------------------------------------------------------------ generate
     @torch.inference_mode()
@@ -450,8 +503,13 @@ class HipDecoder(HipBackbone):
                  seed: int = 0, row_base: int = 0, force_full_length: bool = False, callback=None,
                  progress=None, poll_every: int = 16, trace: dict | None = None, use_graph: bool = True,
                  _after_prefill=None, noise: str = "keyed", generator: torch.Generator | None = None,
-                 pad_rows: int = 0):
+                 pad_rows: int = 0, kv_dtype: str | None = None):
         """Zonos.generate (model.py:224-457). Returns the list of int64 [9, T_i] code tensors.
+
+        ``kv_dtype``: "bf16" (default) or "fp8" -- the KV cache as e4m3fn bytes with one power-of-two scale
+        per (row, kv head, key) (zonos_amd.kvlayout): half the KV memory and half the bytes the decode
+        attention streams; the prefill stays exact and only the cached keys / values are quantised. None
+        reads the environment variable ZONOS_KV_DTYPE. Transformer backbone with head_dim 128 only.
 
         ``noise`` picks the race noise of the sampler: "keyed" = the engine's stream keyed by
         (seed, step, draw, row_base + b, codebook, token), independent of batch sharding; "torch" =
@@ -473,6 +531,11 @@ class HipDecoder(HipBackbone):
             raise ValueError(f"Batch size mismatch: {batch_size} * 2 != {prefix_conditioning.shape[0]}")
         if not 0 <= pad_rows < batch_size:
             raise ValueError(f"pad_rows={pad_rows} must leave at least one real utterance of {batch_size}")
+        kv_dtype = resolve_kv_dtype(kv_dtype)
+        if kv_dtype == "fp8" and not (self.kv_fp8_supported and self.cfg.head_dim == 128 and not self.rope_neox):
+            raise ValueError(f"kv_dtype='fp8' needs the transformer backbone with head_dim 128 "
+                             f"({type(self).__name__}, head_dim {self.cfg.head_dim})")
+        self._fp8 = kv_dtype == "fp8"
         _lib.require_gpu(prefix_conditioning, "prefix_conditioning")
         if prefix_conditioning.dim() != 3 or prefix_conditioning.shape[2] != self.cfg.d_model:
             # zk_prefill copies rows of Lc * d_model bf16: a wrong width would read out of bounds

@@ -285,6 +285,7 @@ class HybridDecoder(HybridBackbone, HipDecoder):
     """generate() for the hybrid backbone (the layer loop and state differ from HipDecoder)."""
 
     small_batch_path = False      # the hybrid block sequence has its own _layers (prenorm add + norm)
+    kv_fp8_supported = False      # generate(kv_dtype="fp8") raises ValueError: transformer backbone only
     # the step / prefill sequences are enqueued by the C ABI (zk_hybrid_decode_step / zk_hybrid_prefill);
     # False issues the same sequence from Python (bit-identical; the reference for the test)
     c_step = True
