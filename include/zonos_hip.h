@@ -665,6 +665,68 @@ int zk_loudness_max_blocks(long T, int rate);
 int zk_loudness_gains(const float* wav, int B, long T, const int32_t* lens, int rate, double target_lufs,
                       double* scratch, double* gains, double* loudness, void* stream);
 
+/* ------------------------------------------------------------------ speaker embedding (voice cloning)
+ * zonos/speaker_cloning.py: SpeakerEmbeddingLDA (:387-411) = logFbankCal (:12-34) -> ResNet293 of
+ * SimAMBasicBlock (:63-95, :152-195) -> ASP (:37-60) -> bottleneck Linear (:213, :222) -> LDA Linear
+ * (:404, :411). Activations are channels-last [B][F][T][C] (F mel rows, T frames): x fp32 (residual
+ * stream) and s fp16 (the next conv's input). Channel counts are multiples of 32. */
+/* logFbankCal on 16 kHz mono wav fp32 [B][n], n > 256: MelSpectrogram(n_fft 512, win 400, hop 160,
+ * center + reflect padding, power 2, HTK mel scale, no filter norm), log(x + 1e-6), minus the mean
+ * over time -> out fp32 [B][n_mels][T], T = 1 + n / 160. window fp32 [512] (Hann of 400 zero-padded
+ * centrally), twiddle fp64 [512][2] (cos, sin of 2 pi j / 512), melfb fp32 [257][n_mels]: host tables. */
+int zk_spk_logfbank(const float* wav, int B, int n, const float* window, const double* twiddle,
+                    const float* melfb, int n_mels, float* out, void* stream);
+/* ResNet.conv1 + bn1 + relu (:169-171, :186): feat fp32 [B][F][T] -> x fp32, s fp16 [B][F][T][C];
+ * w fp32 [C][9] (kh major), scale / shift the eval-mode BatchNorm. */
+int zk_spk_stem(const float* feat, int B, int F, int T, const float* w, const float* scale, const float* shift,
+                int C, float* x, uint16_t* s, void* stream);
+/* Conv2d (ks 3 pad 1, or ks 1 pad 0; stride 1 or 2 on both axes; no bias) + eval-mode BatchNorm as fp32
+ * scale / shift [Cout] + optional ReLU. in fp16 [B][Fi][Ti][Cin]; w fp16 packed
+ * [ceil(Cout / 64)][Cin / 32][kh * ks + kw][64][32] (rows past Cout zero); outputs [B][Fo][To][Cout],
+ * Fo = (Fi - 1) / stride + 1: out_s fp16 and / or out_x fp32 (either may be NULL). stats (NULL: none)
+ * fp32 [B][zk_spk_conv_tiles(Fo, To)][3][Cout]: count, mean and sum of squared deviations of out_x
+ * per tile, the input of zk_spk_simam. */
+int zk_spk_conv2d_cl(const uint16_t* in, int B, int Cin, int Fi, int Ti, const uint16_t* w, int Cout, int ks,
+                     int stride, const float* scale, const float* shift, int relu, uint16_t* out_s, float* out_x,
+                     float* stats, void* stream);
+int zk_spk_conv_tiles(int Fo, int To);      /* tiles per clip of a conv with that output size */
+/* SimAMBasicBlock.SimAM + shortcut + relu (:85-95): y fp32 [B][F][T][C] = bn2(conv2), stats its tile
+ * partials (combined in tile order, no atomics); x_out = relu(y sigmoid((y - mu)^2 / (4 (v + 1e-4)) + 0.5)
+ * + shortcut), v = sum (y - mu)^2 / (F T - 1) per (clip, channel); s_out = fp16(x_out). x_out may be
+ * shortcut. moments: fp32 [B][2][C] scratch. */
+int zk_spk_simam(const float* y, int B, int C, int F, int T, const float* stats, const float* shortcut,
+                 float* moments, float* x_out, uint16_t* s_out, void* stream);
+/* ASP.forward (:52-60) on x fp32 [B][F][T][C]: w1 fp32 [att_dim][F * C] and w2 fp32 [F * C][att_dim],
+ * b2 [F * C] with the feature axis permuted from the reference's c F + f to f C + c; bn_scale / bn_shift
+ * the BatchNorm1d(att_dim). hidden: fp32 [B][T][att_dim] scratch. pooled fp32 [B][2 C F] in the
+ * reference's order (mu then sg, feature c F + f). att_dim = 128. */
+int zk_spk_asp(const float* x, int B, int C, int F, int T, const float* w1, const float* b1, const float* bn_scale,
+               const float* bn_shift, const float* w2, const float* b2, int att_dim, float* hidden, float* pooled,
+               void* stream);
+/* bottleneck Linear K -> E (:222) then the LDA Linear E -> L (:411), fp32: emb [B][E], lda [B][L]. */
+int zk_spk_head(const float* pooled, int B, int K, const float* wb, const float* bb, int E, const float* wl,
+                const float* bl, int L, float* emb, float* lda, void* stream);
+/* The whole phase wav -> (embedding, LDA) on a descriptor. blocks is a host array; every other pointer
+ * is device memory. Validated on the host before any launch (zk_last_error()). */
+typedef struct zk_spk_block {
+    int32_t cin, cout, stride, pad_;
+    const uint16_t* w1; const float* scale1; const float* shift1;      /* conv1 3x3 stride s + bn1 */
+    const uint16_t* w2; const float* scale2; const float* shift2;      /* conv2 3x3 + bn2 */
+    const uint16_t* wd; const float* scaled; const float* shiftd;      /* downsample 1x1 stride s + BN, or NULL */
+} zk_spk_block;
+typedef struct zk_spk_desc {
+    int32_t n_mels, c0, nblocks, pool_dim, att_dim, emb_dim, lda_dim, pad_;   /* pool_dim = C F after the last block */
+    const float* window; const double* twiddle; const float* melfb;
+    const float* stem_w; const float* stem_scale; const float* stem_shift;
+    const zk_spk_block* blocks;
+    const float* asp_w1; const float* asp_b1; const float* asp_bn_scale; const float* asp_bn_shift;
+    const float* asp_w2; const float* asp_b2;
+    const float* bott_w; const float* bott_b; const float* lda_w; const float* lda_b;
+} zk_spk_desc;
+size_t zk_speaker_workspace_bytes(const zk_spk_desc* d, int B, int n);    /* 0 + zk_last_error() if invalid */
+int zk_speaker_embed(const zk_spk_desc* d, const float* wav16k, int B, int n, void* workspace,
+                     size_t workspace_bytes, float* emb256, float* lda128, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -86,6 +86,20 @@ class DacDesc(C.Structure):
                ("blocks", DacBlock * DAC_MAXB)]
 
 
+class SpkBlock(C.Structure):
+    _fields_ = [("cin", C.c_int32), ("cout", C.c_int32), ("stride", C.c_int32), ("pad_", C.c_int32),
+                ("w1", P), ("scale1", P), ("shift1", P), ("w2", P), ("scale2", P), ("shift2", P),
+                ("wd", P), ("scaled", P), ("shiftd", P)]
+
+
+class SpkDesc(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("n_mels", "c0", "nblocks", "pool_dim", "att_dim", "emb_dim", "lda_dim",
+                                         "pad_")] + \
+              [(n, P) for n in ("window", "twiddle", "melfb", "stem_w", "stem_scale", "stem_shift", "blocks",
+                                "asp_w1", "asp_b1", "asp_bn_scale", "asp_bn_shift", "asp_w2", "asp_b2",
+                                "bott_w", "bott_b", "lda_w", "lda_b")]
+
+
 # name -> argtypes (all return int status)
 _SIGS = {
     "zk_version": [],
@@ -149,6 +163,13 @@ _SIGS = {
     "zk_resample": [P, I, L, P, I, I, I, I, P, L, P],
     "zk_prefix_cond": [P, I, P, P],
     "zk_loudness_gains": [P, I, L, P, I, C.c_double, P, P, P, P],
+    "zk_spk_logfbank": [P, I, I, P, P, P, I, P, P],
+    "zk_spk_stem": [P, I, I, I, P, P, P, I, P, P, P],
+    "zk_spk_conv2d_cl": [P, I, I, I, I, P, I, I, I, P, P, I, P, P, P, P],
+    "zk_spk_simam": [P, I, I, I, I, P, P, P, P, P, P],
+    "zk_spk_asp": [P, I, I, I, I, P, P, P, P, P, P, I, P, P, P],
+    "zk_spk_head": [P, I, I, P, P, I, P, P, I, P, P, P],
+    "zk_speaker_embed": [C.POINTER(SpkDesc), P, I, I, P, C.c_size_t, P, P, P],
 }
 
 _lib = None
@@ -185,6 +206,10 @@ def load():
     lib.zk_gemm_warm_tiles.argtypes = [I, I, I, I, I, I]
     lib.zk_torch_noise_policy.restype = C.c_int
     lib.zk_torch_noise_policy.argtypes = [L, I, I, C.POINTER(C.c_int), C.POINTER(C.c_long)]
+    lib.zk_spk_conv_tiles.restype = C.c_int
+    lib.zk_spk_conv_tiles.argtypes = [I, I]
+    lib.zk_speaker_workspace_bytes.restype = C.c_size_t
+    lib.zk_speaker_workspace_bytes.argtypes = [C.POINTER(SpkDesc), I, I]
     _lib = lib
     return lib
 
@@ -192,7 +217,7 @@ def load():
 def exported_symbols() -> list[str]:
     return list(_SIGS) + ["zk_last_error", "zk_loudness_max_blocks", "zk_abi_size",
                           "zk_dac_decode_workspace", "zk_dac_resunit_supported", "zk_gemm_warm_tiles",
-                          "zk_torch_noise_policy"]
+                          "zk_torch_noise_policy", "zk_spk_conv_tiles", "zk_speaker_workspace_bytes"]
 
 
 def call(name: str, *args):

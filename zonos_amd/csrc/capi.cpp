@@ -31,7 +31,8 @@ extern "C" int zk_version(void) { return 1; }
 
 // sizeof / offsetof of the by-value ABI structs, so a binding (ctypes here) can verify its
 // layout without a GPU: which = 0 zk_sampling_params, 1 zk_gen_state, 4 ZkCondSeg, 5 ZkCondPlan,
-// 6 zk_step_layer, 7 zk_step_desc, 8 zk_dac_desc; 12-25 sizes / field offsets (see the cases).
+// 6 zk_step_layer, 7 zk_step_desc, 8 zk_dac_desc; 12-25 sizes / field offsets (see the cases);
+// 26-30 zk_spk_block / zk_spk_desc.
 extern "C" long zk_abi_size(int which) {
     switch (which) {
         case 0: return (long)sizeof(zk_sampling_params);
@@ -55,6 +56,11 @@ extern "C" long zk_abi_size(int which) {
         case 23: return (long)offsetof(zk_step_desc, kv_fp8);
         case 24: return (long)offsetof(zk_step_desc, pre_k);
         case 25: return (long)offsetof(zk_step_layer, k_scale);
+        case 26: return (long)sizeof(zk_spk_block);
+        case 27: return (long)sizeof(zk_spk_desc);
+        case 28: return (long)offsetof(zk_spk_block, wd);
+        case 29: return (long)offsetof(zk_spk_desc, blocks);
+        case 30: return (long)offsetof(zk_spk_desc, lda_b);
         default: return -1;
     }
 }

@@ -5,8 +5,8 @@ Kept from the reference: ``Zonos.from_pretrained`` / ``from_local`` / ``generate
 (backbone.layers.{i}.{norm,mixer.in_proj,mixer.out_proj,norm2,mlp.fc1,mlp.fc2},
 backbone.norm_f, embeddings.{k}, heads.{k}). The text/speaker front end
 ``prepare_conditioning`` runs the PrefixConditioner as one HIP launch (zonos_amd/conditioning.py);
-the eSpeak phonemizer and the speaker-embedding network (make_speaker_embedding) are outside this
-engine's scope.
+``make_speaker_embedding`` (model.py:90-95) runs the speaker-embedding network of voice cloning as HIP
+kernels (zonos_amd/speaker.py, built on first use). The eSpeak phonemizer is outside this engine's scope.
 """
 from __future__ import annotations
 
@@ -41,6 +41,7 @@ class Zonos:
         else:
             self.engine = HipDecoder(EngineConfig.from_backbone_config(bc), state_dict, self.device)
         self._autoencoder = autoencoder
+        self.spk_clone_model = None
         pc = {k[len("prefix_conditioner."):]: v for k, v in state_dict.items() if k.startswith("prefix_conditioner.")}
         self.prefix_conditioner = None
         if pc:
@@ -103,8 +104,14 @@ class Zonos:
             raise ValueError("this model was loaded without prefix_conditioner.* weights")
         return self.prefix_conditioner.prepare_conditioning(cond_dict, uncond_dict)
 
-    def make_speaker_embedding(self, wav, sr):
-        raise NotImplementedError("speaker embedding (zonos/speaker_cloning.py) is outside the HIP engine's scope")
+    def make_speaker_embedding(self, wav: torch.Tensor, sr: int) -> torch.Tensor:
+        """model.py:90-95: the LDA-projected speaker embedding of a clip, [1, 1, 128] bf16. The network
+        (zonos_amd.speaker.SpeakerEmbeddingLDA) is built on the first call and kept."""
+        if self.spk_clone_model is None:
+            from .speaker import SpeakerEmbeddingLDA
+            self.spk_clone_model = SpeakerEmbeddingLDA(device=self.device)
+        _, spk_embedding = self.spk_clone_model(wav.to(self.device), sr)
+        return spk_embedding.unsqueeze(0).bfloat16()
 
     @torch.inference_mode()
     def generate(self, prefix_conditioning: torch.Tensor, audio_prefix_codes: torch.Tensor | None = None,

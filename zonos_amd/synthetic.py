@@ -179,3 +179,67 @@ def conditioning(batch: int, Lc: int, D: int, seed: int = 1, device="cpu") -> to
 def prefix_codes(batch: int, P: int, seed: int = 3, device="cpu") -> torch.Tensor:
     g = torch.Generator().manual_seed(seed)
     return torch.randint(0, 1024, (batch, 9, P), generator=g).to(device)
+
+
+def speaker_state_dict(in_planes: int = 64, blocks=(10, 20, 64, 3), seed: int = 0, n_mels: int = 80,
+                       embd_dim: int = 256, lda_dim: int = 128, branch_gain: float = 0.2):
+    """(network state dict, LDA state dict) of the speaker-embedding model in the reference's key layout
+    (zonos/speaker_cloning.py ResNet293_based :198-223 and the LDA nn.Linear :402-405), seeded on the CPU
+    generator so that every machine regenerates the same bytes. Conv weights are He-scaled; conv2 of each
+    block carries ``branch_gain`` on top, so the residual stream of 97 blocks stays in range. BatchNorm
+    weight in 0.8-1.2, bias and running_mean ~ N(0, 0.1^2), running_var in 0.7-1.3: the BN path is not an
+    identity."""
+    g = torch.Generator().manual_seed(seed)
+    sd = {}
+
+    def conv(key, cout, cin, k, gain=1.0):
+        sd[key] = torch.randn(cout, cin, k, k, generator=g) * (gain * math.sqrt(2.0 / (cin * k * k)))
+
+    def bn(prefix, c):
+        sd[prefix + "weight"] = 0.8 + 0.4 * torch.rand(c, generator=g)
+        sd[prefix + "bias"] = 0.1 * torch.randn(c, generator=g)
+        sd[prefix + "running_mean"] = 0.1 * torch.randn(c, generator=g)
+        sd[prefix + "running_var"] = 0.7 + 0.6 * torch.rand(c, generator=g)
+        sd[prefix + "num_batches_tracked"] = torch.tensor(1000, dtype=torch.long)
+
+    conv("front.conv1.weight", in_planes, 1, 3)
+    bn("front.bn1.", in_planes)
+    cin = in_planes
+    for layer, nb in enumerate(blocks, 1):
+        cout = in_planes << (layer - 1)
+        for i in range(nb):
+            p = f"front.layer{layer}.{i}."
+            stride = 2 if (layer > 1 and i == 0) else 1
+            conv(p + "conv1.weight", cout, cin, 3)
+            bn(p + "bn1.", cout)
+            conv(p + "conv2.weight", cout, cout, 3, branch_gain)
+            bn(p + "bn2.", cout)
+            if stride != 1 or cin != cout:
+                conv(p + "downsample.0.weight", cout, cin, 1, math.sqrt(0.5))
+                bn(p + "downsample.1.", cout)
+            cin = cout
+    feat = cin * (n_mels // 8)
+    sd["pooling.attention.0.weight"] = torch.randn(128, feat, 1, generator=g) / math.sqrt(feat)
+    sd["pooling.attention.0.bias"] = 0.1 * torch.randn(128, generator=g)
+    sd["pooling.attention.2.weight"] = 0.8 + 0.4 * torch.rand(128, generator=g)
+    sd["pooling.attention.2.bias"] = 0.1 * torch.randn(128, generator=g)
+    sd["pooling.attention.2.running_mean"] = 0.1 * torch.randn(128, generator=g)
+    sd["pooling.attention.2.running_var"] = 0.7 + 0.6 * torch.rand(128, generator=g)
+    sd["pooling.attention.2.num_batches_tracked"] = torch.tensor(1000, dtype=torch.long)
+    sd["pooling.attention.3.weight"] = torch.randn(feat, 128, 1, generator=g) * (2.0 / math.sqrt(128))
+    sd["pooling.attention.3.bias"] = 0.1 * torch.randn(feat, generator=g)
+    sd["bottleneck.weight"] = torch.randn(embd_dim, 2 * feat, generator=g) / math.sqrt(2 * feat)
+    sd["bottleneck.bias"] = 0.1 * torch.randn(embd_dim, generator=g)
+    lda = {"weight": torch.randn(lda_dim, embd_dim, generator=g) / math.sqrt(embd_dim),
+           "bias": 0.1 * torch.randn(lda_dim, generator=g)}
+    return sd, lda
+
+
+def state_dict_sha256(sd: dict) -> str:
+    """sha256 over the tensors' bytes in key order (what the speaker fixtures pin the weights with)."""
+    import hashlib
+    h = hashlib.sha256()
+    for k in sorted(sd):
+        h.update(k.encode())
+        h.update(sd[k].contiguous().numpy().tobytes())
+    return h.hexdigest()
