@@ -180,7 +180,11 @@ int zk_qkv_rope(const float* part, int nsplit, int R, int S, int H, int Hkv, int
  *         over 128-key blocks split across `nsplit` workgroups per (row, kv head)
  *         (nsplit <= Smax/128; work: fp32 [R][Hkv][nsplit][8 + 4*hd] when nsplit > 1).
  * prefill: S queries per row at positions 0..S-1, causal (is_causal=S>1), K and V from the cache.
- * Output bf16 [rows][H*hd]. */
+ * Output bf16 [rows][H*hd].
+ * Every zk_attn_decode* entry, bf16 or FP8 cache, fails before any launch, with zk_last_error starting
+ * with its own name, on hd != 128, a GQA group above 4, Smax <= 0 or not a multiple of 128 (_q_part: of
+ * 32), nsplit out of range, a missing work buffer, a NULL cache, scale or output pointer, a NULL q, or
+ * (fused forms) NULL part / freqs or gemm_nsplit outside [1, 8]. */
 int zk_attn_decode(const void* q, const void* k_cache, const void* vt_cache, int R, int H, int Hkv,
                    int hd, int Smax, int ctx0, const int32_t* ctx_dev, float* work, int nsplit,
                    void* out, const int32_t* skip, void* stream);
@@ -197,7 +201,7 @@ int zk_attn_decode_qkv(const float* part, int gemm_nsplit, const float* freqs, v
 /* zk_attn_decode_qkv with the split-KV partials merged inside the launch (no k_attn_combine):
  * counters = uint32 [R][Hkv], zeroed once before the first launch (each launch adds nsplit per
  * (row, kv head); the workgroup drawing the last ticket merges). nsplit == 1 or counters == NULL
- * is zk_attn_decode_qkv. Same results as the two-launch form, bit for bit. */
+ * launches what zk_attn_decode_qkv launches. Same results as the two-launch form, bit for bit. */
 int zk_attn_decode_qkv_sc(const float* part, int gemm_nsplit, const float* freqs, void* k_cache,
                           void* vt_cache, int R, int H, int Hkv, int hd, int Smax, int ctx0,
                           const int32_t* ctx_dev, float* work, int nsplit, uint32_t* counters, void* out,

@@ -50,6 +50,53 @@ def test_argument_validation_without_gpu(lib):
     assert b"zk_gemm_bf16" in lib.zk_last_error()
 
 
+# the decode-attention entries' parameters, in ABI order (include/zonos_hip.h)
+_DIMS = ["R", "H", "Hkv", "hd", "Smax", "ctx0", "ctx_dev", "work", "nsplit"]
+_FUSED = ["part", "gemm_nsplit", "freqs"]
+ATTN_DECODE_ENTRIES = {
+    "zk_attn_decode": ["q", "k", "v", *_DIMS, "out", "skip", "stream"],
+    "zk_attn_decode_qkv": [*_FUSED, "k", "v", *_DIMS, "out", "rope_neox", "skip", "stream"],
+    "zk_attn_decode_qkv_sc": [*_FUSED, "k", "v", *_DIMS, "counters", "out", "rope_neox", "skip", "stream"],
+    "zk_attn_decode_qkv_part": [*_FUSED, "k", "v", *_DIMS, "rope_neox", "skip", "stream"],
+    "zk_attn_decode_f8": ["q", "k", "v", "k_scale", "v_scale", *_DIMS, "out", "skip", "stream"],
+    "zk_attn_decode_qkv_f8": [*_FUSED, "k", "v", "k_scale", "v_scale", *_DIMS, "counters", "out", "skip", "stream"],
+    "zk_attn_decode_q_part": ["q", "k", "v", *_DIMS, "skip", "stream"],
+}
+
+
+def test_attention_decode_entries_refuse_bad_arguments_without_gpu(lib):
+    """Every decode-attention entry refuses, on the host and under its own name, a null K or V cache, a null
+    output (where it writes one), null FP8 scales, head_dim 64, Smax 0 / 100, nsplit 0, nsplit > 1 without
+    the work buffer and (fused forms) gemm_nsplit 0 / AT_MAXGS + 1. All other pointers are a dummy host
+    buffer: nothing is launched, because a check fails first."""
+    import ctypes as C
+    src = open(os.path.join(REPO, "zonos_amd", "csrc", "attn_common.h")).read()
+    maxgs = int(re.search(r"constexpr int AT_MAXGS = (\d+);", src).group(1))
+    buf = C.create_string_buffer(64)
+    lib.zk_last_error.restype = C.c_char_p
+    ints = dict(R=2, H=4, Hkv=1, hd=128, Smax=256, ctx0=1, nsplit=2, gemm_nsplit=1, rope_neox=0)
+
+    def refused(name, params, **bad):
+        args = [bad[p] if p in bad else ints[p] if p in ints else None if p == "stream" else buf for p in params]
+        rc = getattr(lib, name)(*[C.c_int(a) if isinstance(a, int) else a for a in args])
+        err = lib.zk_last_error()
+        assert rc != 0, (name, bad)
+        assert err.startswith(name.encode() + b":"), (name, bad, err)
+        assert b"launch failed" not in err, (name, bad, err)      # a check refused it, not the runtime
+
+    for name, params in ATTN_DECODE_ENTRIES.items():
+        cases = [dict(k=None), dict(v=None), dict(hd=64), dict(Smax=0), dict(Smax=100), dict(nsplit=0),
+                 dict(nsplit=2, work=None)]
+        cases += [dict(out=None)] if "out" in params else []
+        cases += [dict(k_scale=None), dict(v_scale=None)] if "k_scale" in params else []
+        cases += [dict(gemm_nsplit=0), dict(gemm_nsplit=maxgs + 1)] if "gemm_nsplit" in params else []
+        for bad in cases:
+            refused(name, params, **bad)
+    # one split (no in-launch combine to do): still this entry's own checks and name
+    refused("zk_attn_decode_qkv_sc", ATTN_DECODE_ENTRIES["zk_attn_decode_qkv_sc"], nsplit=1, hd=64)
+    refused("zk_attn_decode_qkv_sc", ATTN_DECODE_ENTRIES["zk_attn_decode_qkv_sc"], nsplit=1, k=None)
+
+
 def test_prefill_rejects_short_kv_cache_without_gpu(lib):
     """zk_prefill / zk_hybrid_prefill refuse a descriptor whose KV cache (smax keys) is shorter than
     the context of the last decode step (Lc + Ld), before any launch: the decode attention's context

@@ -177,11 +177,7 @@ ZK_DEV void patch_kv(KVFrag& f, const uint32_t* s_kn, const uint16_t* s_vn, int 
 // reduces the split-K slabs of its own 4 query heads + 1 KV head (768 columns), applies RoPE,
 // keeps q in LDS and (the split that owns the newest key) stores the new K / V^T entries
 // before the key loop reads them. One launch per layer instead of two.
-// COMB (nsplit > 1): the splits of one (row, kv head) combine in this launch instead of in
-// k_attn_combine -- each workgroup publishes its partial (m, l, O) (stores drained, agent-scope
-// release) and takes a ticket on cnt[row][kv head]; the workgroup drawing the last ticket of the
-// launch (tickets are monotonic: the count is a multiple of nsplit before every launch) acquires
-// and merges all nsplit partials exactly as k_attn_combine does. Saves the combine launch.
+// COMB: the in-launch combine of attn_finish.
 // sum of the in_proj split-K slabs of one RoPE pair (d0, d1) of a column block, left to right
 // in fp32 like k_qkv_rope: every slab load issued before the first add
 template <int NS, bool NEOX>
@@ -223,6 +219,7 @@ ZK_DEV void slab_pair_n(const float* p, size_t slab, int ns, int d0, int d1, flo
 // The pointer is read once, at the top of the kernel (ZK_ATT_PROF_PTR, by a scalar load before any data
 // load), so a stamp is a register-sourced store: re-reading the global at each stamp put a vector load
 // behind the key blocks in flight, and the wait for it drained them (the stamps moved the kernel).
+// attn_finish reads it again for its own stamps 4..7: by then the key loop is over.
 #ifdef ZK_ATT_PROF
 __device__ uint64_t* g_att_prof;
 #define ZK_ATT_PROF_PTR                                                                                     \
@@ -260,6 +257,118 @@ struct __attribute__((aligned(16))) AttnSmem {
     uint16_t s_vn[128];      // new value
     int s_last;              // COMB: this workgroup merges
 };
+
+// The nsplit partials (m, l, O) of one (row, kv head) at `base` -> channels d, d + 1 of the group's head j,
+// normalised and packed: max over the splits first, then L, o0, o1 summed left to right.
+ZK_DEV uint32_t attn_combine_pair(const float* base, int nsplit, int j, int d) {
+    constexpr int HD = 128;
+    float M = -INFINITY;
+    for (int sp = 0; sp < nsplit; ++sp) M = fmaxf(M, base[sp * AT_STR + j]);
+    float L = 0.f, o0 = 0.f, o1 = 0.f;
+    for (int sp = 0; sp < nsplit; ++sp) {
+        const float* p = base + sp * AT_STR;
+        const float c = (p[j] == -INFINITY) ? 0.f : __expf(p[j] - M);
+        L += p[AT_G + j] * c;
+        o0 += p[2 * AT_G + j * HD + d] * c;
+        o1 += p[2 * AT_G + j * HD + d + 1] * c;
+    }
+    const float inv = 1.0f / L;
+    return pack2(o0 * inv, o1 * inv);
+}
+
+// The end of a decode-attention workgroup (split, kv head g, row r), for the bf16 and the FP8 cache alike: the
+// 4 waves merge their (m, l, O) through LDS, then nsplit == 1 writes the normalised bf16 output, nsplit > 1 the
+// split's partial to `work`.
+// COMB (nsplit > 1): the splits of one (row, kv head) combine in this launch instead of in k_attn_combine --
+// each workgroup publishes its partial (stores drained, agent-scope release) and takes a ticket on
+// cnt[row][kv head]; the workgroup drawing the last ticket of the launch (tickets are monotonic: the count is a
+// multiple of nsplit before every launch) acquires and merges all nsplit partials. Saves the combine launch.
+template <bool COMB, class Bar>
+ZK_DEV void attn_finish(AttnSmem& sm, const Bar& bar, const AttnState& st, int split, int nsplit, int g, int r,
+                        int H, int Hkv, float* work, bf16_t* out, uint32_t* cnt) {
+    constexpr int HD = 128;
+    ZK_ATT_PROF_PTR;
+    const size_t blk = (size_t)r * Hkv + g;
+    const int G = H / Hkv;
+    const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int ln = lane & 15, lg = lane >> 4;
+    auto& s_m = sm.s_m;
+    auto& s_l = sm.s_l;
+    auto& s_o = sm.s_o;
+    auto& s_last = sm.s_last;
+    // merge the 4 waves
+    if (lg == 0) { s_m[w][ln] = st.m; s_l[w][ln] = st.l; }
+    bar();
+    const float M = fmaxf(fmaxf(s_m[0][ln], s_m[1][ln]), fmaxf(s_m[2][ln], s_m[3][ln]));
+    const float cw = (st.m == -INFINITY) ? 0.f : __expf(st.m - M);
+    if (ln < AT_G) {
+#pragma unroll
+        for (int dt = 0; dt < 8; ++dt)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) s_o[w][ln][dt * 16 + lg * 4 + i] = st.o[dt][i] * cw;
+    }
+    bar();
+    ZK_ATT_STAMP(4);
+    if (nsplit == 1) {
+        // normalised output for the G heads: thread -> (head, 2 channels)
+        for (int i = threadIdx.x; i < G * HD / 2; i += 256) {
+            const int h = i / (HD / 2), d = (i % (HD / 2)) * 2;
+            float Mh = -INFINITY;
+            for (int k = 0; k < 4; ++k) Mh = fmaxf(Mh, s_m[k][h]);
+            float L = 0.f;
+            for (int k = 0; k < 4; ++k) L += (s_m[k][h] == -INFINITY) ? 0.f : s_l[k][h] * __expf(s_m[k][h] - Mh);
+            const float o0 = s_o[0][h][d] + s_o[1][h][d] + s_o[2][h][d] + s_o[3][h][d];
+            const float o1 = s_o[0][h][d + 1] + s_o[1][h][d + 1] + s_o[2][h][d + 1] + s_o[3][h][d + 1];
+            const float inv = 1.0f / L;
+            *reinterpret_cast<uint32_t*>(out + (size_t)r * H * HD + (size_t)(g * G + h) * HD + d) =
+                pack2(o0 * inv, o1 * inv);
+        }
+        ZK_ATT_STAMP(5);
+        ZK_ATT_HWID();
+        return;
+    }
+    float* wp = work + (blk * nsplit + split) * AT_STR;
+    for (int i = threadIdx.x; i < AT_G * HD; i += 256) {
+        const int h = i / HD, d = i % HD;
+        wp[2 * AT_G + i] = s_o[0][h][d] + s_o[1][h][d] + s_o[2][h][d] + s_o[3][h][d];
+    }
+    if (threadIdx.x < AT_G) {
+        const int h = threadIdx.x;
+        float Mh = -INFINITY;
+        for (int k = 0; k < 4; ++k) Mh = fmaxf(Mh, s_m[k][h]);
+        float L = 0.f;
+        for (int k = 0; k < 4; ++k) L += (s_m[k][h] == -INFINITY) ? 0.f : s_l[k][h] * __expf(s_m[k][h] - Mh);
+        wp[h] = Mh;
+        wp[AT_G + h] = L;
+    }
+    if constexpr (COMB) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // every storing wave drains
+        bar();
+        if (threadIdx.x == 0) {
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // keep the fence's wait (ROCm 7.2)
+            const uint32_t old = __hip_atomic_fetch_add(cnt + blk, 1u, __ATOMIC_RELAXED,
+                                                        __HIP_MEMORY_SCOPE_AGENT);
+            s_last = ((old + 1) % (uint32_t)nsplit) == 0;
+        }
+        bar();
+        ZK_ATT_STAMP(5);
+        if (!s_last) return;
+        if (threadIdx.x == 0) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+        bar();
+        ZK_ATT_STAMP(6);
+        const float* base = work + blk * nsplit * AT_STR;
+        for (int i = threadIdx.x; i < G * HD / 2; i += 256) {
+            const int j = i / (HD / 2), d = (i % (HD / 2)) * 2;
+            *reinterpret_cast<uint32_t*>(out + (size_t)r * H * HD + (size_t)(g * G + j) * HD + d) =
+                attn_combine_pair(base, nsplit, j, d);
+        }
+        ZK_ATT_STAMP(7);
+    }
+}
 
 // One workgroup of 4 waves (threads 0..255) = one (split, kv head g, row r). `bar` is the barrier
 // among those 4 waves (__syncthreads in k_attn_decode); `issued` runs right after the first key
@@ -314,13 +423,9 @@ ZK_DEV void attn_decode_wg(AttnSmem& sm, const Bar& bar, const Issued& issued, i
         asm volatile("" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
     }
-    auto& s_m = sm.s_m;
-    auto& s_l = sm.s_l;
-    auto& s_o = sm.s_o;
     auto& s_q = sm.s_q;
     auto& s_kn = sm.s_kn;
     auto& s_vn = sm.s_vn;
-    auto& s_last = sm.s_last;
     const int nkb = (ctx + AT_KB - 1) / AT_KB;
     const int kb0 = (int)((long)split * nkb / nsplit), kb1 = (int)((long)(split + 1) * nkb / nsplit);
     const int G = H / Hkv;
@@ -479,89 +584,7 @@ ZK_DEV void attn_decode_wg(AttnSmem& sm, const Bar& bar, const Issued& issued, i
         if (t < HD / 2) *reinterpret_cast<uint32_t*>(kb + k_off(pos, t >> 2) + ((2 * t) & 7)) = s_kn[t];
         else if (t < HD / 2 + HD) reinterpret_cast<uint16_t*>(vb)[v_off(pos, t - HD / 2)] = s_vn[t - HD / 2];
     }
-    // merge the 4 waves
-    if (lg == 0) { s_m[w][ln] = st.m; s_l[w][ln] = st.l; }
-    bar();
-    const float M = fmaxf(fmaxf(s_m[0][ln], s_m[1][ln]), fmaxf(s_m[2][ln], s_m[3][ln]));
-    const float cw = (st.m == -INFINITY) ? 0.f : __expf(st.m - M);
-    if (ln < AT_G) {
-#pragma unroll
-        for (int dt = 0; dt < 8; ++dt)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) s_o[w][ln][dt * 16 + lg * 4 + i] = st.o[dt][i] * cw;
-    }
-    bar();
-    ZK_ATT_STAMP(4);
-    if (nsplit == 1) {
-        // normalised output for the G heads: thread -> (head, 2 channels)
-        for (int i = threadIdx.x; i < G * HD / 2; i += 256) {
-            const int h = i / (HD / 2), d = (i % (HD / 2)) * 2;
-            float Mh = -INFINITY;
-            for (int k = 0; k < 4; ++k) Mh = fmaxf(Mh, s_m[k][h]);
-            float L = 0.f;
-            for (int k = 0; k < 4; ++k) L += (s_m[k][h] == -INFINITY) ? 0.f : s_l[k][h] * __expf(s_m[k][h] - Mh);
-            const float o0 = s_o[0][h][d] + s_o[1][h][d] + s_o[2][h][d] + s_o[3][h][d];
-            const float o1 = s_o[0][h][d + 1] + s_o[1][h][d + 1] + s_o[2][h][d + 1] + s_o[3][h][d + 1];
-            const float inv = 1.0f / L;
-            *reinterpret_cast<uint32_t*>(out + (size_t)r * H * HD + (size_t)(g * G + h) * HD + d) =
-                pack2(o0 * inv, o1 * inv);
-        }
-        ZK_ATT_STAMP(5);
-        ZK_ATT_HWID();
-        return;
-    }
-    float* wp = work + (((size_t)r * Hkv + g) * nsplit + split) * AT_STR;
-    for (int i = threadIdx.x; i < AT_G * HD; i += 256) {
-        const int h = i / HD, d = i % HD;
-        wp[2 * AT_G + i] = s_o[0][h][d] + s_o[1][h][d] + s_o[2][h][d] + s_o[3][h][d];
-    }
-    if (threadIdx.x < AT_G) {
-        const int h = threadIdx.x;
-        float Mh = -INFINITY;
-        for (int k = 0; k < 4; ++k) Mh = fmaxf(Mh, s_m[k][h]);
-        float L = 0.f;
-        for (int k = 0; k < 4; ++k) L += (s_m[k][h] == -INFINITY) ? 0.f : s_l[k][h] * __expf(s_m[k][h] - Mh);
-        wp[h] = Mh;
-        wp[AT_G + h] = L;
-    }
-    if constexpr (COMB) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // every storing wave drains
-        bar();
-        if (threadIdx.x == 0) {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // keep the fence's wait (ROCm 7.2)
-            const uint32_t old = __hip_atomic_fetch_add(cnt + (size_t)r * Hkv + g, 1u, __ATOMIC_RELAXED,
-                                                        __HIP_MEMORY_SCOPE_AGENT);
-            s_last = ((old + 1) % (uint32_t)nsplit) == 0;
-        }
-        bar();
-        ZK_ATT_STAMP(5);
-        if (!s_last) return;
-        if (threadIdx.x == 0) {
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        bar();
-        ZK_ATT_STAMP(6);
-        const float* base = work + ((size_t)r * Hkv + g) * nsplit * AT_STR;
-        for (int i = threadIdx.x; i < G * HD / 2; i += 256) {       // k_attn_combine's arithmetic
-            const int j = i / (HD / 2), d = (i % (HD / 2)) * 2;
-            float M = -INFINITY;
-            for (int sp = 0; sp < nsplit; ++sp) M = fmaxf(M, base[sp * AT_STR + j]);
-            float L = 0.f, o0 = 0.f, o1 = 0.f;
-            for (int sp = 0; sp < nsplit; ++sp) {
-                const float* p = base + sp * AT_STR;
-                const float c = (p[j] == -INFINITY) ? 0.f : __expf(p[j] - M);
-                L += p[AT_G + j] * c;
-                o0 += p[2 * AT_G + j * HD + d] * c;
-                o1 += p[2 * AT_G + j * HD + d + 1] * c;
-            }
-            const float inv = 1.0f / L;
-            *reinterpret_cast<uint32_t*>(out + (size_t)r * H * HD + (size_t)(g * G + j) * HD + d) =
-                pack2(o0 * inv, o1 * inv);
-        }
-        ZK_ATT_STAMP(7);
-    }
+    attn_finish<COMB>(sm, bar, st, split, nsplit, g, r, H, Hkv, work, out, cnt);
 }
 
 // B = 1 decode attention over 32-key slices (zk_attn_decode_q_part): q comes from the in_proj GEMV's

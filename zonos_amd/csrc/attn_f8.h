@@ -1,7 +1,7 @@
 // Decode attention over the FP8 (OCP e4m3fn) KV cache and the quantiser that fills it after prefill
-// (included by backbone.hip). Same block / wave / merge structure as attn_decode_wg (attn_common.h): 128-key
-// blocks, 32 keys per wave, the same split rule and wave merge, the same mfma_f32_16x16x32_bf16 steps
-// (attn_step), so the result is bit for bit that of the bf16 kernel on the dequantised cache.
+// (included by backbone.hip). Same block / wave structure as attn_decode_wg (attn_common.h): 128-key
+// blocks, 32 keys per wave, the same split rule, the same mfma_f32_16x16x32_bf16 steps (attn_step) and the
+// same tail (attn_finish), so the result is bit for bit that of the bf16 kernel on the dequantised cache.
 //
 // Cache layout per (row, kv head), 32-key slices of 4 KB (zonos_amd.kvlayout), each lane's load 16 B:
 //   K8: [slice][h 2][kp 2][lane 64][q 2][8]  lane = 16*lg + ln holds key 8*(ln>>2) + 4h + (ln&3),
@@ -153,8 +153,8 @@ ZK_DEV void patch_kv8(KV8Frag& f, const Attn8Smem& s8, int key_base, int pos, in
     }
 }
 
-// qkv_prologue and attn_finish restate attn_decode_wg's slab-reduce / RoPE loop and its wave-merge tail
-// line for line; the bf16 kernel keeps its own inline copies so that its generated code stays what it was.
+// qkv_prologue restates attn_decode_wg's slab-reduce / RoPE loop line for line; the bf16 kernel keeps its own
+// inline copy (with the pre-issued slab form) so that its generated code stays what it was.
 // The in_proj epilogue of one workgroup, pairs first, first + 256, ... of [0, (G + 2) * 64): q of heads
 // g*G.. (RoPE) into sm.s_q, then the new key (RoPE) into sm.s_kn and the new value into sm.s_vn. prow: the
 // row's first slab, fc: the position's (cos, sin) row.
@@ -193,99 +193,6 @@ ZK_DEV void qkv_prologue(AttnSmem& sm, int first, const float* prow, size_t slab
         } else {
             s_vn[d0] = f2bf(a);
             s_vn[d1] = f2bf(bb);
-        }
-    }
-}
-
-// The end of a decode-attention workgroup: the 4 waves merge their (m, l, O) through LDS, then nsplit == 1
-// writes the normalised bf16 output, nsplit > 1 the split's partial to `work` and, COMB, the workgroup
-// drawing the launch's last ticket on cnt[row][kv head] merges all partials (k_attn_combine's arithmetic).
-template <bool COMB, class Bar>
-ZK_DEV void attn_finish(AttnSmem& sm, const Bar& bar, const AttnState& st, int split, int nsplit, int g, int r,
-                        int H, int Hkv, float* work, bf16_t* out, uint32_t* cnt) {
-    constexpr int HD = 128;
-    auto& s_m = sm.s_m;
-    auto& s_l = sm.s_l;
-    auto& s_o = sm.s_o;
-    auto& s_last = sm.s_last;
-    const int G = H / Hkv;
-    const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int ln = lane & 15, lg = lane >> 4;
-    // merge the 4 waves
-    if (lg == 0) { s_m[w][ln] = st.m; s_l[w][ln] = st.l; }
-    bar();
-    const float M = fmaxf(fmaxf(s_m[0][ln], s_m[1][ln]), fmaxf(s_m[2][ln], s_m[3][ln]));
-    const float cw = (st.m == -INFINITY) ? 0.f : __expf(st.m - M);
-    if (ln < AT_G) {
-#pragma unroll
-        for (int dt = 0; dt < 8; ++dt)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) s_o[w][ln][dt * 16 + lg * 4 + i] = st.o[dt][i] * cw;
-    }
-    bar();
-    if (nsplit == 1) {
-        // normalised output for the G heads: thread -> (head, 2 channels)
-        for (int i = threadIdx.x; i < G * HD / 2; i += 256) {
-            const int h = i / (HD / 2), d = (i % (HD / 2)) * 2;
-            float Mh = -INFINITY;
-            for (int k = 0; k < 4; ++k) Mh = fmaxf(Mh, s_m[k][h]);
-            float L = 0.f;
-            for (int k = 0; k < 4; ++k) L += (s_m[k][h] == -INFINITY) ? 0.f : s_l[k][h] * __expf(s_m[k][h] - Mh);
-            const float o0 = s_o[0][h][d] + s_o[1][h][d] + s_o[2][h][d] + s_o[3][h][d];
-            const float o1 = s_o[0][h][d + 1] + s_o[1][h][d + 1] + s_o[2][h][d + 1] + s_o[3][h][d + 1];
-            const float inv = 1.0f / L;
-            *reinterpret_cast<uint32_t*>(out + (size_t)r * H * HD + (size_t)(g * G + h) * HD + d) =
-                pack2(o0 * inv, o1 * inv);
-        }
-        return;
-    }
-    float* wp = work + (((size_t)r * Hkv + g) * nsplit + split) * AT_STR;
-    for (int i = threadIdx.x; i < AT_G * HD; i += 256) {
-        const int h = i / HD, d = i % HD;
-        wp[2 * AT_G + i] = s_o[0][h][d] + s_o[1][h][d] + s_o[2][h][d] + s_o[3][h][d];
-    }
-    if (threadIdx.x < AT_G) {
-        const int h = threadIdx.x;
-        float Mh = -INFINITY;
-        for (int k = 0; k < 4; ++k) Mh = fmaxf(Mh, s_m[k][h]);
-        float L = 0.f;
-        for (int k = 0; k < 4; ++k) L += (s_m[k][h] == -INFINITY) ? 0.f : s_l[k][h] * __expf(s_m[k][h] - Mh);
-        wp[h] = Mh;
-        wp[AT_G + h] = L;
-    }
-    if constexpr (COMB) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // every storing wave drains
-        bar();
-        if (threadIdx.x == 0) {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // keep the fence's wait (ROCm 7.2)
-            const uint32_t old = __hip_atomic_fetch_add(cnt + (size_t)r * Hkv + g, 1u, __ATOMIC_RELAXED,
-                                                        __HIP_MEMORY_SCOPE_AGENT);
-            s_last = ((old + 1) % (uint32_t)nsplit) == 0;
-        }
-        bar();
-        if (!s_last) return;
-        if (threadIdx.x == 0) {
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        bar();
-        const float* base = work + ((size_t)r * Hkv + g) * nsplit * AT_STR;
-        for (int i = threadIdx.x; i < G * HD / 2; i += 256) {       // k_attn_combine's arithmetic
-            const int j = i / (HD / 2), d = (i % (HD / 2)) * 2;
-            float M = -INFINITY;
-            for (int sp = 0; sp < nsplit; ++sp) M = fmaxf(M, base[sp * AT_STR + j]);
-            float L = 0.f, o0 = 0.f, o1 = 0.f;
-            for (int sp = 0; sp < nsplit; ++sp) {
-                const float* p = base + sp * AT_STR;
-                const float c = (p[j] == -INFINITY) ? 0.f : __expf(p[j] - M);
-                L += p[AT_G + j] * c;
-                o0 += p[2 * AT_G + j * HD + d] * c;
-                o1 += p[2 * AT_G + j * HD + d + 1] * c;
-            }
-            const float inv = 1.0f / L;
-            *reinterpret_cast<uint32_t*>(out + (size_t)r * H * HD + (size_t)(g * G + j) * HD + d) =
-                pack2(o0 * inv, o1 * inv);
         }
     }
 }
@@ -432,18 +339,6 @@ __global__ __launch_bounds__(256) void k_kv_quantize_e4m3(const bf16_t* ksrc, co
 }  // namespace
 
 // ------------------------------------------------------------------ entries
-#define ZK_F8_REQUIRE(name)                                                                                   \
-    ZK_REQUIRE(hd == 128, name ": head_dim %d unsupported (128 only)", hd);                                   \
-    ZK_REQUIRE(H % Hkv == 0 && H / Hkv <= AT_G, name ": GQA group %d > %d", H / Hkv, AT_G);                   \
-    ZK_REQUIRE(Smax > 0 && Smax % AT_KB == 0, name ": Smax=%d must be a multiple of %d", Smax, AT_KB);        \
-    ZK_REQUIRE(nsplit >= 1 && nsplit <= Smax / AT_KB, name ": nsplit=%d out of [1, %d]", nsplit, Smax / AT_KB); \
-    ZK_REQUIRE(nsplit == 1 || work != nullptr, name ": nsplit > 1 needs the work buffer");                    \
-    ZK_REQUIRE(k8 != nullptr && v8 != nullptr && k_scale != nullptr && v_scale != nullptr && out != nullptr,  \
-               name ": null cache, scale or output buffer")
-
-// non-temporal KV loads by the KV_NT_BYTES rule on the FP8 byte count (K8 + V8)
-static bool f8_kvnt(int R, int Hkv, int Smax, int hd) { return (double)R * Hkv * Smax * hd * 2 >= KV_NT_BYTES; }
-
 extern "C" int zk_kv_quantize_e4m3(const void* k_src, const void* vt_src, int R, int Hkv, int hd, int S, int Smax_src,
                                    void* k8, void* v8, void* k_scale, void* v_scale, int Smax, void* stream) {
     ZK_REQUIRE(hd == 128, "zk_kv_quantize_e4m3: head_dim %d unsupported (128 only)", hd);
@@ -467,42 +362,24 @@ extern "C" int zk_attn_decode_f8(const void* q, const void* k8, const void* v8, 
                                  const void* v_scale, int R, int H, int Hkv, int hd, int Smax, int ctx0,
                                  const int32_t* ctx_dev, float* work, int nsplit, void* out, const int32_t* skip,
                                  void* stream) {
-    ZK_F8_REQUIRE("zk_attn_decode_f8");
-    ZK_REQUIRE(q != nullptr, "zk_attn_decode_f8: null q");
-    const float scale = 1.0f / sqrtf((float)hd);
-    auto kern = f8_kvnt(R, Hkv, Smax, hd) ? k_attn_decode_f8<false, true, false> : k_attn_decode_f8<false, false, false>;
-    hipLaunchKernelGGL(kern, dim3(nsplit, Hkv, R), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)q, (uint8_t*)k8,
-                       (uint8_t*)v8, (uint8_t*)k_scale, (uint8_t*)v_scale, R, H, Hkv, Smax, ctx0, ctx_dev, work, scale,
-                       (bf16_t*)out, skip, nullptr, 0, nullptr, nullptr);
-    ZK_CHECK_LAUNCH("zk_attn_decode_f8");
-    if (nsplit > 1) {
-        hipLaunchKernelGGL(k_attn_combine, dim3(H, R), dim3(64), 0, (hipStream_t)stream, work, H, Hkv, nsplit,
-                           (bf16_t*)out, skip);
-        ZK_CHECK_LAUNCH("zk_attn_combine");
-    }
-    return 0;
+    AttnDecode a{"zk_attn_decode_f8", R, H, Hkv, hd, Smax, ctx0, ctx_dev, work, nsplit, out, skip, stream};
+    a.q = q;
+    auto kern = kv_nt(R, Hkv, Smax, hd, 1) ? k_attn_decode_f8<false, true, false> : k_attn_decode_f8<false, false, false>;
+    return attn_decode_launch(a, kern, (uint8_t*)k8, (uint8_t*)v8, (uint8_t*)k_scale, (uint8_t*)v_scale);
 }
 
 extern "C" int zk_attn_decode_qkv_f8(const float* part, int gemm_nsplit, const float* freqs, void* k8, void* v8,
                                      void* k_scale, void* v_scale, int R, int H, int Hkv, int hd, int Smax, int ctx0,
                                      const int32_t* ctx_dev, float* work, int nsplit, uint32_t* counters, void* out,
                                      const int32_t* skip, void* stream) {
-    ZK_F8_REQUIRE("zk_attn_decode_qkv_f8");
-    ZK_REQUIRE(part != nullptr && freqs != nullptr && gemm_nsplit >= 1 && gemm_nsplit <= AT_MAXGS,
-               "zk_attn_decode_qkv_f8: bad arguments (gemm_nsplit=%d, max %d)", gemm_nsplit, AT_MAXGS);
-    const float scale = 1.0f / sqrtf((float)hd);
-    const bool nt = f8_kvnt(R, Hkv, Smax, hd), comb = nsplit > 1 && counters != nullptr;
-    auto kern = comb ? (nt ? k_attn_decode_f8<true, true, true> : k_attn_decode_f8<true, false, true>)
-                     : (nt ? k_attn_decode_f8<true, true, false> : k_attn_decode_f8<true, false, false>);
-    hipLaunchKernelGGL(kern, dim3(nsplit, Hkv, R), dim3(256), 0, (hipStream_t)stream, nullptr, (uint8_t*)k8,
-                       (uint8_t*)v8, (uint8_t*)k_scale, (uint8_t*)v_scale, R, H, Hkv, Smax, ctx0, ctx_dev, work, scale,
-                       (bf16_t*)out, skip, part, gemm_nsplit, freqs, counters);
-    ZK_CHECK_LAUNCH("zk_attn_decode_qkv_f8");
-    if (nsplit > 1 && !comb) {
-        hipLaunchKernelGGL(k_attn_combine, dim3(H, R), dim3(64), 0, (hipStream_t)stream, work, H, Hkv, nsplit,
-                           (bf16_t*)out, skip);
-        ZK_CHECK_LAUNCH("zk_attn_combine");
-    }
-    return 0;
+    AttnDecode a{"zk_attn_decode_qkv_f8", R, H, Hkv, hd, Smax, ctx0, ctx_dev, work, nsplit, out, skip, stream};
+    a.fused = true;
+    a.part = part;
+    a.gemm_nsplit = gemm_nsplit;
+    a.freqs = freqs;
+    a.counters = counters;
+    const bool nt = kv_nt(R, Hkv, Smax, hd, 1);
+    auto kern = a.comb() ? (nt ? k_attn_decode_f8<true, true, true> : k_attn_decode_f8<true, false, true>)
+                         : (nt ? k_attn_decode_f8<true, true, false> : k_attn_decode_f8<true, false, false>);
+    return attn_decode_launch(a, kern, (uint8_t*)k8, (uint8_t*)v8, (uint8_t*)k_scale, (uint8_t*)v_scale);
 }
-#undef ZK_F8_REQUIRE

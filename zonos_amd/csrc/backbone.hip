@@ -433,19 +433,8 @@ __global__ __launch_bounds__(64) void k_attn_combine(const float* work, int H, i
     const int h = blockIdx.x, r = blockIdx.y;
     const int G = H / Hkv, g = h / G, j = h % G;
     const float* base = work + ((size_t)r * Hkv + g) * nsplit * AT_STR;
-    float M = -INFINITY;
-    for (int s = 0; s < nsplit; ++s) M = fmaxf(M, base[s * AT_STR + j]);
-    float L = 0.f, o0 = 0.f, o1 = 0.f;
     const int d = threadIdx.x * 2;
-    for (int s = 0; s < nsplit; ++s) {
-        const float* p = base + s * AT_STR;
-        const float c = (p[j] == -INFINITY) ? 0.f : __expf(p[j] - M);
-        L += p[AT_G + j] * c;
-        o0 += p[2 * AT_G + j * HD + d] * c;
-        o1 += p[2 * AT_G + j * HD + d + 1] * c;
-    }
-    const float inv = 1.0f / L;
-    *reinterpret_cast<uint32_t*>(out + (size_t)r * H * HD + (size_t)h * HD + d) = pack2(o0 * inv, o1 * inv);
+    *reinterpret_cast<uint32_t*>(out + (size_t)r * H * HD + (size_t)h * HD + d) = attn_combine_pair(base, nsplit, j, d);
 }
 
 // ------------------------------------------------------------------ prefill attention (causal)
@@ -645,28 +634,74 @@ extern "C" int zk_qkv_rope(const float* part, int nsplit, int R, int S, int H, i
     return 0;
 }
 
-extern "C" int zk_attn_decode(const void* q, const void* k_cache, const void* vt_cache, int R, int H, int Hkv,
-                              int hd, int Smax, int ctx0, const int32_t* ctx_dev, float* work, int nsplit,
-                              void* out, const int32_t* skip, void* stream) {
-    ZK_REQUIRE(hd == 128, "zk_attn_decode: head_dim %d unsupported (128 only)", hd);
-    ZK_REQUIRE(H % Hkv == 0 && H / Hkv <= AT_G, "zk_attn_decode: GQA group %d > %d", H / Hkv, AT_G);
-    ZK_REQUIRE(Smax % AT_KB == 0, "zk_attn_decode: Smax=%d must be a multiple of %d", Smax, AT_KB);
-    ZK_REQUIRE(nsplit >= 1 && nsplit <= Smax / AT_KB, "zk_attn_decode: nsplit=%d out of [1, %d]", nsplit,
-               Smax / AT_KB);
-    ZK_REQUIRE(nsplit == 1 || work != nullptr, "zk_attn_decode: nsplit > 1 needs the work buffer");
-    const float scale = 1.0f / sqrtf((float)hd);
-    const bool kvnt = (double)R * Hkv * Smax * hd * 4 >= KV_NT_BYTES;
-    auto kern = kvnt ? k_attn_decode<false, false, true> : k_attn_decode<false, false, false>;
-    hipLaunchKernelGGL(kern, dim3(nsplit, Hkv, R), dim3(256), 0, (hipStream_t)stream,
-                       (const bf16_t*)q, (bf16_t*)k_cache, (bf16_t*)vt_cache, R, H, Hkv, Smax, ctx0, ctx_dev, work,
-                       scale, (bf16_t*)out, skip, nullptr, 0, nullptr, nullptr);
-    ZK_CHECK_LAUNCH("zk_attn_decode");
-    if (nsplit > 1) {
-        hipLaunchKernelGGL(k_attn_combine, dim3(H, R), dim3(64), 0, (hipStream_t)stream, work, H, Hkv, nsplit,
-                           (bf16_t*)out, skip);
+// non-temporal KV loads (ld_kv): one launch streams >= KV_NT_BYTES of cache, K and V together
+static bool kv_nt(int R, int Hkv, int Smax, int hd, int elem_bytes) {
+    return (double)R * Hkv * Smax * hd * elem_bytes * 2 >= KV_NT_BYTES;
+}
+
+// One launch of the k_attn_decode / k_attn_decode_f8 family, grid (nsplit, Hkv, R) x 256 threads: the arguments
+// every entry has (brace-initialised in this order), then the ones that tell the forms apart.
+struct AttnDecode {
+    const char* name;      // the extern "C" entry the caller called: every message starts with it
+    int R, H, Hkv, hd, Smax, ctx0;
+    const int32_t* ctx_dev;
+    float* work;
+    int nsplit;
+    void* out;
+    const int32_t* skip;
+    void* stream;
+    const void* q = nullptr;            // the query rows, or (fused) the in_proj slabs and the RoPE table:
+    bool fused = false;
+    const float* part = nullptr;
+    int gemm_nsplit = 0;
+    const float* freqs = nullptr;
+    bool part_only = false;             // the splits' partials stay in `work` for a later kernel (no out)
+    uint32_t* counters = nullptr;       // fused, nsplit > 1: the splits combine in the launch
+    bool comb() const { return fused && !part_only && nsplit > 1 && counters != nullptr; }
+};
+
+// Every check of the family, then the launch of `kern` (the entry's instantiation) and, where the splits were
+// neither combined in the launch nor asked for as partials, k_attn_combine. `cache` are the kernel's cache
+// arguments: K and V^T, then the two scale arrays of the FP8 cache.
+template <class Kern, class... Cache>
+static int attn_decode_launch(const AttnDecode& a, Kern kern, Cache... cache) {
+    const int min_split = a.part_only ? 2 : 1;
+    ZK_REQUIRE(a.hd == 128, "%s: head_dim %d unsupported (128 only)", a.name, a.hd);
+    ZK_REQUIRE(a.Hkv > 0 && a.H % a.Hkv == 0 && a.H / a.Hkv <= AT_G, "%s: GQA group %d > %d", a.name,
+               a.Hkv > 0 ? a.H / a.Hkv : 0, AT_G);
+    ZK_REQUIRE(a.Smax > 0 && a.Smax % AT_KB == 0, "%s: Smax=%d must be a multiple of %d", a.name, a.Smax, AT_KB);
+    ZK_REQUIRE(a.nsplit >= min_split && a.nsplit <= a.Smax / AT_KB, "%s: nsplit=%d out of [%d, %d]", a.name, a.nsplit,
+               min_split, a.Smax / AT_KB);
+    ZK_REQUIRE(a.nsplit == 1 || a.work != nullptr,
+               a.part_only ? "%s: null work buffer" : "%s: nsplit > 1 needs the work buffer", a.name);
+    ZK_REQUIRE(((cache != nullptr) && ...) && (a.part_only || a.out != nullptr),
+               sizeof...(Cache) > 2 ? "%s: null cache, scale or output buffer" : "%s: null cache or output buffer",
+               a.name);
+    if (a.fused)
+        ZK_REQUIRE(a.part != nullptr && a.freqs != nullptr && a.gemm_nsplit >= 1 && a.gemm_nsplit <= AT_MAXGS,
+                   "%s: bad arguments (gemm_nsplit=%d, max %d)", a.name, a.gemm_nsplit, AT_MAXGS);
+    else
+        ZK_REQUIRE(a.q != nullptr, "%s: null q", a.name);
+    const float scale = 1.0f / sqrtf((float)a.hd);
+    hipLaunchKernelGGL(kern, dim3(a.nsplit, a.Hkv, a.R), dim3(256), 0, (hipStream_t)a.stream, (const bf16_t*)a.q,
+                       cache..., a.R, a.H, a.Hkv, a.Smax, a.ctx0, a.ctx_dev, a.work, scale, (bf16_t*)a.out, a.skip,
+                       a.part, a.gemm_nsplit, a.freqs, a.comb() ? a.counters : nullptr);
+    ZK_CHECK_LAUNCH(a.name);
+    if (a.nsplit > 1 && !a.comb() && !a.part_only) {
+        hipLaunchKernelGGL(k_attn_combine, dim3(a.H, a.R), dim3(64), 0, (hipStream_t)a.stream, a.work, a.H, a.Hkv,
+                           a.nsplit, (bf16_t*)a.out, a.skip);
         ZK_CHECK_LAUNCH("zk_attn_combine");
     }
     return 0;
+}
+
+extern "C" int zk_attn_decode(const void* q, const void* k_cache, const void* vt_cache, int R, int H, int Hkv,
+                              int hd, int Smax, int ctx0, const int32_t* ctx_dev, float* work, int nsplit,
+                              void* out, const int32_t* skip, void* stream) {
+    AttnDecode a{"zk_attn_decode", R, H, Hkv, hd, Smax, ctx0, ctx_dev, work, nsplit, out, skip, stream};
+    a.q = q;
+    auto kern = kv_nt(R, Hkv, Smax, hd, 2) ? k_attn_decode<false, false, true> : k_attn_decode<false, false, false>;
+    return attn_decode_launch(a, kern, (bf16_t*)k_cache, (bf16_t*)vt_cache);
 }
 
 // the fused decode attention instantiation: RoPE form, non-temporal KV loads, in-launch combine, and the
@@ -681,68 +716,48 @@ static auto fused_attn_kernel(bool neox, bool kvnt, int gemm_nsplit) {
                 : (kvnt ? k_attn_decode<true, false, true, COMB, 0> : k_attn_decode<true, false, false, COMB, 0>);
 }
 
+// the fused bf16 launch of `a` (zk_attn_decode_qkv, _qkv_part, _qkv_sc)
+static int attn_decode_qkv(AttnDecode a, const float* part, int gemm_nsplit, const float* freqs, void* k_cache,
+                           void* vt_cache, int rope_neox) {
+    a.fused = true;
+    a.part = part;
+    a.gemm_nsplit = gemm_nsplit;
+    a.freqs = freqs;
+    const bool nt = kv_nt(a.R, a.Hkv, a.Smax, a.hd, 2);
+    auto kern = a.comb() ? fused_attn_kernel<true>(rope_neox, nt, gemm_nsplit)
+                         : fused_attn_kernel<false>(rope_neox, nt, gemm_nsplit);
+    return attn_decode_launch(a, kern, (bf16_t*)k_cache, (bf16_t*)vt_cache);
+}
+
 extern "C" int zk_attn_decode_qkv(const float* part, int gemm_nsplit, const float* freqs, void* k_cache,
                                   void* vt_cache, int R, int H, int Hkv, int hd, int Smax, int ctx0,
                                   const int32_t* ctx_dev, float* work, int nsplit, void* out, int rope_neox,
                                   const int32_t* skip, void* stream) {
-    ZK_REQUIRE(hd == 128, "zk_attn_decode_qkv: head_dim %d unsupported (128 only)", hd);
-    ZK_REQUIRE(H % Hkv == 0 && H / Hkv <= AT_G, "zk_attn_decode_qkv: GQA group %d > %d", H / Hkv, AT_G);
-    ZK_REQUIRE(Smax % AT_KB == 0, "zk_attn_decode_qkv: Smax=%d must be a multiple of %d", Smax, AT_KB);
-    ZK_REQUIRE(nsplit >= 1 && nsplit <= Smax / AT_KB, "zk_attn_decode_qkv: nsplit=%d out of [1, %d]", nsplit,
-               Smax / AT_KB);
-    ZK_REQUIRE(nsplit == 1 || work != nullptr, "zk_attn_decode_qkv: nsplit > 1 needs the work buffer");
-    ZK_REQUIRE(part != nullptr && freqs != nullptr && gemm_nsplit >= 1 && gemm_nsplit <= AT_MAXGS,
-               "zk_attn_decode_qkv: bad arguments (gemm_nsplit=%d, max %d)", gemm_nsplit, AT_MAXGS);
-    const float scale = 1.0f / sqrtf((float)hd);
-    const bf16_t* dbgq = nullptr;
-    const bool kvnt = (double)R * Hkv * Smax * hd * 4 >= KV_NT_BYTES;
-    auto kern = fused_attn_kernel<false>(rope_neox, kvnt, gemm_nsplit);
-    hipLaunchKernelGGL(kern, dim3(nsplit, Hkv, R), dim3(256), 0, (hipStream_t)stream, dbgq, (bf16_t*)k_cache,
-                       (bf16_t*)vt_cache, R, H, Hkv, Smax, ctx0, ctx_dev, work, scale, (bf16_t*)out, skip, part,
-                       gemm_nsplit, freqs, nullptr);
-    ZK_CHECK_LAUNCH("zk_attn_decode_qkv");
-    if (nsplit > 1) {
-        hipLaunchKernelGGL(k_attn_combine, dim3(H, R), dim3(64), 0, (hipStream_t)stream, work, H, Hkv, nsplit,
-                           (bf16_t*)out, skip);
-        ZK_CHECK_LAUNCH("zk_attn_combine");
-    }
-    return 0;
+    const AttnDecode a{"zk_attn_decode_qkv", R, H, Hkv, hd, Smax, ctx0, ctx_dev, work, nsplit, out, skip, stream};
+    return attn_decode_qkv(a, part, gemm_nsplit, freqs, k_cache, vt_cache, rope_neox);
 }
 
 extern "C" int zk_attn_decode_qkv_part(const float* part, int gemm_nsplit, const float* freqs, void* k_cache,
                                        void* vt_cache, int R, int H, int Hkv, int hd, int Smax, int ctx0,
                                        const int32_t* ctx_dev, float* work, int nsplit, int rope_neox,
                                        const int32_t* skip, void* stream) {
-    ZK_REQUIRE(hd == 128, "zk_attn_decode_qkv_part: head_dim %d unsupported (128 only)", hd);
-    ZK_REQUIRE(H % Hkv == 0 && H / Hkv <= AT_G, "zk_attn_decode_qkv_part: GQA group %d > %d", H / Hkv, AT_G);
-    ZK_REQUIRE(Smax % AT_KB == 0, "zk_attn_decode_qkv_part: Smax=%d must be a multiple of %d", Smax, AT_KB);
-    ZK_REQUIRE(nsplit >= 2 && nsplit <= Smax / AT_KB, "zk_attn_decode_qkv_part: nsplit=%d out of [2, %d]", nsplit,
-               Smax / AT_KB);
-    ZK_REQUIRE(work != nullptr, "zk_attn_decode_qkv_part: null work buffer");
-    ZK_REQUIRE(part != nullptr && freqs != nullptr && gemm_nsplit >= 1 && gemm_nsplit <= AT_MAXGS,
-               "zk_attn_decode_qkv_part: bad arguments (gemm_nsplit=%d, max %d)", gemm_nsplit, AT_MAXGS);
-    const float scale = 1.0f / sqrtf((float)hd);
-    const bool kvnt = (double)R * Hkv * Smax * hd * 4 >= KV_NT_BYTES;
-    auto kern = fused_attn_kernel<false>(rope_neox, kvnt, gemm_nsplit);
-    hipLaunchKernelGGL(kern, dim3(nsplit, Hkv, R), dim3(256), 0, (hipStream_t)stream, nullptr, (bf16_t*)k_cache,
-                       (bf16_t*)vt_cache, R, H, Hkv, Smax, ctx0, ctx_dev, work, scale, nullptr, skip, part,
-                       gemm_nsplit, freqs, nullptr);
-    ZK_CHECK_LAUNCH("zk_attn_decode_qkv_part");
-    return 0;
+    AttnDecode a{"zk_attn_decode_qkv_part", R, H, Hkv, hd, Smax, ctx0, ctx_dev, work, nsplit, nullptr, skip, stream};
+    a.part_only = true;
+    return attn_decode_qkv(a, part, gemm_nsplit, freqs, k_cache, vt_cache, rope_neox);
 }
 
 extern "C" int zk_attn_decode_q_part(const void* q, const void* k_cache, const void* vt_cache, int R, int H,
                                      int Hkv, int hd, int Smax, int ctx0, const int32_t* ctx_dev, float* work,
                                      int nsplit, const int32_t* skip, void* stream) {
     ZK_REQUIRE(hd == 128, "zk_attn_decode_q_part: head_dim %d unsupported (128 only)", hd);
-    ZK_REQUIRE(H % Hkv == 0 && H / Hkv <= AT_G, "zk_attn_decode_q_part: GQA group %d > %d", H / Hkv, AT_G);
+    ZK_REQUIRE(Hkv > 0 && H % Hkv == 0 && H / Hkv <= AT_G, "zk_attn_decode_q_part: GQA group %d > %d",
+               Hkv > 0 ? H / Hkv : 0, AT_G);
     ZK_REQUIRE(Smax % 32 == 0 && Smax > 0, "zk_attn_decode_q_part: Smax=%d must be a multiple of 32", Smax);
     ZK_REQUIRE(nsplit >= 1 && nsplit <= 64, "zk_attn_decode_q_part: nsplit=%d out of [1, 64]", nsplit);
     ZK_REQUIRE(q != nullptr && work != nullptr && k_cache != nullptr && vt_cache != nullptr,
                "zk_attn_decode_q_part: null buffer");
     const float scale = 1.0f / sqrtf((float)hd);
-    const bool kvnt = (double)R * Hkv * Smax * hd * 4 >= KV_NT_BYTES;
-    auto kern = kvnt ? k_attn_decode_qs<true> : k_attn_decode_qs<false>;
+    auto kern = kv_nt(R, Hkv, Smax, hd, 2) ? k_attn_decode_qs<true> : k_attn_decode_qs<false>;
     hipLaunchKernelGGL(kern, dim3(nsplit, Hkv, R), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)q,
                        (const bf16_t*)k_cache, (const bf16_t*)vt_cache, H, Hkv, Smax, ctx0, ctx_dev, work, scale, skip);
     ZK_CHECK_LAUNCH("zk_attn_decode_q_part");
@@ -753,25 +768,9 @@ extern "C" int zk_attn_decode_qkv_sc(const float* part, int gemm_nsplit, const f
                                      void* vt_cache, int R, int H, int Hkv, int hd, int Smax, int ctx0,
                                      const int32_t* ctx_dev, float* work, int nsplit, uint32_t* counters, void* out,
                                      int rope_neox, const int32_t* skip, void* stream) {
-    if (nsplit == 1 || counters == nullptr)
-        return zk_attn_decode_qkv(part, gemm_nsplit, freqs, k_cache, vt_cache, R, H, Hkv, hd, Smax, ctx0, ctx_dev,
-                                  work, nsplit, out, rope_neox, skip, stream);
-    ZK_REQUIRE(hd == 128, "zk_attn_decode_qkv_sc: head_dim %d unsupported (128 only)", hd);
-    ZK_REQUIRE(H % Hkv == 0 && H / Hkv <= AT_G, "zk_attn_decode_qkv_sc: GQA group %d > %d", H / Hkv, AT_G);
-    ZK_REQUIRE(Smax % AT_KB == 0, "zk_attn_decode_qkv_sc: Smax=%d must be a multiple of %d", Smax, AT_KB);
-    ZK_REQUIRE(nsplit >= 1 && nsplit <= Smax / AT_KB, "zk_attn_decode_qkv_sc: nsplit=%d out of [1, %d]", nsplit,
-               Smax / AT_KB);
-    ZK_REQUIRE(work != nullptr, "zk_attn_decode_qkv_sc: nsplit > 1 needs the work buffer");
-    ZK_REQUIRE(part != nullptr && freqs != nullptr && gemm_nsplit >= 1 && gemm_nsplit <= AT_MAXGS,
-               "zk_attn_decode_qkv_sc: bad arguments (gemm_nsplit=%d, max %d)", gemm_nsplit, AT_MAXGS);
-    const float scale = 1.0f / sqrtf((float)hd);
-    const bool kvnt = (double)R * Hkv * Smax * hd * 4 >= KV_NT_BYTES;
-    auto kern = fused_attn_kernel<true>(rope_neox, kvnt, gemm_nsplit);
-    hipLaunchKernelGGL(kern, dim3(nsplit, Hkv, R), dim3(256), 0, (hipStream_t)stream, nullptr, (bf16_t*)k_cache,
-                       (bf16_t*)vt_cache, R, H, Hkv, Smax, ctx0, ctx_dev, work, scale, (bf16_t*)out, skip, part,
-                       gemm_nsplit, freqs, counters);
-    ZK_CHECK_LAUNCH("zk_attn_decode_qkv_sc");
-    return 0;
+    AttnDecode a{"zk_attn_decode_qkv_sc", R, H, Hkv, hd, Smax, ctx0, ctx_dev, work, nsplit, out, skip, stream};
+    a.counters = counters;
+    return attn_decode_qkv(a, part, gemm_nsplit, freqs, k_cache, vt_cache, rope_neox);
 }
 
 #ifdef ZK_ATT_PROF

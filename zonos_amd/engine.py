@@ -104,8 +104,8 @@ def attn_splits_for(R: int, Hkv: int, smax: int, target_blocks: int = 512) -> in
     workgroup per (row, kv head) (512 workgroups, no combine pass) reads 5.4-5.7 TB/s at
     ctx 1.7-3k vs 4.5-4.7 with 2 splits. Small batches split the keys to fill the CUs, but
     each split must cover >= 2048 keys of the cache: the combine launch costs ~6 us, more than
-    it saves below that (B=1, 10 s: 1.294 ms per decode step unsplit vs 1.353 with 10 splits,
-    tools/c2_attn_ab.sh)."""
+    it saves below that (B=1, 10 s: 1.294 ms per decode step unsplit vs 1.353 with 10 splits;
+    such A/Bs run through tools/gpu_ab.sh)."""
     want = -(-target_blocks // (R * Hkv))
     cap = max(1, -(-smax // 2048))
     return max(1, min(want, cap, smax // 128))

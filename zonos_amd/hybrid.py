@@ -197,7 +197,7 @@ class HybridBackbone:
     def splits(self, R: int) -> dict:
         """decode_splits plus the Mamba projections. in_proj (N = 8512, K = 2048) without split-K: 133
         workgroups, no fp32 slab round trip for k_mamba_step (c5 decode step 4.67 vs 4.87 ms with 2 splits,
-        4.96 with 4; tools/c5_split_ab.sh; round 4 with 80-column split-2 workgroups: the GEMM 15.3 -> 12.8 us
+        4.96 with 4; profiles/r2_s3_c5_split_ab.txt; round 4 with 80-column split-2 workgroups: the GEMM 15.3 -> 12.8 us
         alone, the step 4.34 -> 4.39 ms, profiles/r4s3_hyb_inp_split_ab.txt). The attention out_proj 4-way and
         the heads unsplit, as the transformer engine: 4.645 vs 4.670 ms."""
         c = self.cfg
