@@ -137,6 +137,28 @@ def test_gemm_warm_up_stays_inside_packed_image(lib):
     assert seen_narrow
 
 
+def test_gemm_warm_word_round_trip(lib):
+    """The packed warm-up word (warm.h: chunks, NG, compute waves, grid tiles past N) is packed by
+    zk_gemm_warm_desc and unpacked by warm_unit's accessors, which zk_gemm_warm_tiles runs on the host: the
+    tiles it counts are exactly the grid's 16-column tiles that hold a column < N, for workgroups of 2, 3,
+    4 and 5 compute waves and with a non-zero number of grid tiles past N."""
+    lib.zk_gemm_warm_tiles.restype = ctypes.c_int
+    # (M, N, K, nsplit) -> compute waves per workgroup (the rule of gemm.hip's ws_ncw), grid tiles past N
+    cases = [((128, 8512, 2048, 1), 3, 2), ((128, 9234, 2048, 2), 5, 2), ((72, 3000, 512, 1), 2, 0),
+             ((128, 3072, 2048, 4), 4, 0), ((24, 1000, 2048, 2), 4, 1), ((128, 2048, 2048, 4), 2, 0)]
+    for (M, N, K, nsplit), nw, excess in cases:
+        tiles = (N + 15) // 16
+        gx = -(-N // (16 * nw))
+        assert gx * nw - tiles == excess, (N, nw)          # the case is what its comment says
+        for chunks in (1, 2, 4, 40):                       # more chunks than the K slice has: clamped, same tiles
+            assert lib.zk_gemm_warm_tiles(M, N, K, nsplit, 0, chunks) == tiles, (M, N, K, nsplit, chunks)
+    # (a width or an excess lost in the word would show: N = 8512 unpacked as 4 waves counts 178 x 4 - 2 = 710
+    # tiles, without its excess 534, for an image of 532)
+    # outside k_gemm_ws's regime (M <= 16; 128 chunks per slice; a prefill M): no warm-up
+    for M, N, K, nsplit in ((16, 3072, 2048, 4), (128, 2048, 8192, 1), (300, 3072, 2048, 1)):
+        assert lib.zk_gemm_warm_tiles(M, N, K, nsplit, 0, 2) == 0
+
+
 def test_split_selection_batch_invariant():
     from zonos_amd.engine import _split_for
     for N, K in ((3072, 2048), (2048, 2048), (2048, 8192), (9234, 2048)):

@@ -86,7 +86,12 @@ def test_delay_pattern_golden():
                                           (1100, 256, 512, 1), (2048, 384, 2048, 1), (1024, 1152, 128, 1),
                                           # prefill shapes with >= 256 tiles of 256 x 256 (k_gemm_pf): ragged
                                           # last row block, N not a multiple of 256 (hybrid in_proj), K = 8192
-                                          (16400, 4096, 1024, 1), (8300, 8512, 512, 1), (9000, 2048, 8192, 1)])
+                                          (16400, 4096, 1024, 1), (8300, 8512, 512, 1), (9000, 2048, 8192, 1),
+                                          # the boundaries of the launch plan (gemm.hip gemm_plan): the last M of
+                                          # k_gemv_rk, the first of k_gemm_ws, its 64 / 65-row forms (65 rows: 2-wave
+                                          # workgroups), the first M of k_gemm; N no multiple of a workgroup's columns
+                                          (16, 80, 256, 1), (17, 80, 256, 2), (64, 80, 128, 1), (65, 144, 256, 1),
+                                          (129, 80, 256, 1)])
 def test_gemm_vs_fp32(M, N, K, nsplit):
     from zonos_amd._lib import call, ptr, stream_ptr
     g = torch.Generator(device="cpu").manual_seed(M + N)
@@ -173,7 +178,9 @@ def test_pack_weights_layout():
 
 
 @pytest.mark.parametrize("M,Fd,D", [(130, 256, 512), (2, 256, 512), (40, 256, 512), (128, 512, 2048),
-                                    (3, 512, 2048), (1030, 256, 512), (8200, 4096, 1024)])
+                                    (3, 512, 2048), (1030, 256, 512), (8200, 4096, 1024),
+                                    # M <= 16 on k_gemm_ws: the one K slice (256) k_gemv_rk has no SwiGLU form for
+                                    (16, 48, 256)])
 def test_gemm_swiglu(M, Fd, D):
     from zonos_amd._lib import call, ptr, stream_ptr
     g = torch.Generator(device="cpu").manual_seed(1)

@@ -22,7 +22,42 @@
 #include "../../include/zonos_hip.h"
 #include "warm.h"
 #include <algorithm>
+#include <initializer_list>
 #include <stdlib.h>
+#include <type_traits>
+
+// Build switches of this file (DESIGN.md "Build switches"; -D overrides, zonos_amd.build.build_variant)
+#ifndef ZK_WS_PF
+#define ZK_WS_PF 4                 // k_gemm_ws weight chunks in flight per compute wave, mode 1 (SwiGLU fc1)
+#endif
+#ifndef ZK_WS_PF0
+#define ZK_WS_PF0 3                // ... and mode 0 (the split-K slab GEMMs)
+#endif
+#ifndef ZK_WS_NCW
+#define ZK_WS_NCW 4                // k_gemm_ws compute waves (16-column tiles) per workgroup
+#endif
+#ifndef ZK_WS_NARROW
+#define ZK_WS_NARROW 2             // fewest compute waves of the narrow workgroups (2 or 3; 0: off)
+#endif
+#ifndef ZK_WS_WIDE
+#define ZK_WS_WIDE 5               // compute waves of the wide workgroups for slab GEMMs with > 256 64-column tiles (0: off)
+#endif
+#ifndef ZK_WS_NARROW_BELOW
+#define ZK_WS_NARROW_BELOW 192     // ... when the 64-column grid has fewer workgroups than this
+#endif
+// k_gemv_f: waves per workgroup (one- / two-tile layouts, half-tile layout), k-steps in flight per wave
+#ifndef ZK_GF_NW
+#define ZK_GF_NW 4
+#endif
+#ifndef ZK_GF_NWH
+#define ZK_GF_NWH 8
+#endif
+#ifndef ZK_GF_PF
+#define ZK_GF_PF 8
+#endif
+#ifndef ZK_GF_PFLN
+#define ZK_GF_PFLN 12              // k-steps in flight of the B = 1 LayerNorm-prologue one-tile GEMV (in_proj):
+#endif                             // c2 step 1.045-1.048 vs 1.051-1.053 ms at 8, 1.054-1.055 at 16 (r3_b1_gemv_pf_ab)
 
 namespace {
 
@@ -211,14 +246,8 @@ constexpr int WS_NB = 6;         // LDS ring slots (16 KB each)
 constexpr int WS_DA = 4;         // activation chunks in flight (loader); WS_NB >= WS_DA + 2
 constexpr int WS_OCC = 1;        // workgroups per CU the kernel is sized for
 constexpr int WS_NLD = 4;        // loader waves (each moves 1/WS_NLD of every chunk)
-#ifndef ZK_WS_PF
-#define ZK_WS_PF 4
-#endif
 constexpr int WS_LDSPF = 1;      // chunks published ahead of the one being multiplied
 constexpr int WS_PF = ZK_WS_PF;  // weight chunks in flight per compute wave: the SwiGLU fc1 (mode 1)
-#ifndef ZK_WS_PF0
-#define ZK_WS_PF0 3
-#endif
 constexpr int WS_PF0 = ZK_WS_PF0; // ... and the split-K slab GEMMs (mode 0): 3 measured faster for the
                                   // in_proj / out_proj / fc2 shapes, 4 for fc1 (profiles/r3s2_gemm_pf_ab.txt)
 
@@ -243,12 +272,13 @@ ZK_DEV void vm_wait() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N_) : "memory")
 // (2*MT pieces per chunk): each loader's counted vmcnt waits assume NP pieces per younger chunk, so
 // a loader with fewer would pass the publishing barrier with pieces of that chunk still in flight
 // (NCW = 5 at MT = 8: 3 loaders would split 16 pieces 6 / 5 / 5 -- 2 loaders split them 8 / 8).
-template <int NCW, int MT>
-constexpr int ws_nld() {
-    int n = NCW + WS_NLD > 8 ? 8 - NCW : WS_NLD;
-    while (n > 1 && n < 2 * MT && (2 * MT) % n != 0) --n;
+constexpr int ws_nld(int ncw, int mt) {
+    int n = ncw + WS_NLD > 8 ? 8 - ncw : WS_NLD;
+    while (n > 1 && n < 2 * mt && (2 * mt) % n != 0) --n;
     return n;
 }
+template <int NCW, int MT>
+constexpr int ws_nld() { return ws_nld(NCW, MT); }
 template <int MODE, int NCH, int PF, int MT, int NCW = 4, int NG = 1, int NB = (NCW > 5 ? 1 : 2)>
 __global__ __launch_bounds__(64 * (NCW + ws_nld<NCW, MT>()), WS_OCC) void k_gemm_ws(const bf16_t* __restrict__ A, long lda,
                                                            const bf16_t* __restrict__ W, int M, int N, int K,
@@ -1035,36 +1065,66 @@ extern "C" int zk_pack_weights(const void* w, int N, int K, void* out, void* str
     return 0;
 }
 
-#ifndef ZK_WS_NCW
-#define ZK_WS_NCW 4                // k_gemm_ws compute waves (16-column tiles) per workgroup
-#endif
-#ifndef ZK_WS_NARROW
-#define ZK_WS_NARROW 2             // fewest compute waves of the narrow workgroups (2 or 3; 0: off)
-#endif
-#ifndef ZK_WS_WIDE
-#define ZK_WS_WIDE 5               // compute waves of the wide workgroups for slab GEMMs with > 256 64-column tiles (0: off)
-#endif
-#define ZK_WS_WIDE_W (ZK_WS_WIDE > 0 ? ZK_WS_WIDE : 1)
-#ifndef ZK_WS_NARROW_BELOW
-#define ZK_WS_NARROW_BELOW 192     // ... when the 64-column grid has fewer workgroups than this
-#endif
-
-// k_gemm_ws regime of zk_gemm_bf16_warm below (16 < M <= 128 or M <= 16 with K/nsplit % 128 != 0)
-static bool ws_regime(int M, int K, int nsplit) {
-    if (M <= 16 && (K / nsplit) % 128 == 0) return false;
-    return M <= BM && K / nsplit / BK <= 32;
+extern "C" int zk_permute_fc1(const void* w_fc1, int F, int D, void* w_out, void* stream) {
+    ZK_REQUIRE(F % 8 == 0 && D % 8 == 0, "zk_permute_fc1: F=%d D=%d", F, D);
+    hipLaunchKernelGGL(k_permute_fc1, dim3(2 * F), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)w_fc1, F, D,
+                       (bf16_t*)w_out);
+    ZK_CHECK_LAUNCH("zk_permute_fc1");
+    return 0;
 }
 
+// ------------------------------------------------------------------ host side: one plan per launch
+// Every entry checks its arguments, asks a pure function for the launch's plan (kernel family, the
+// family's template selectors as run-time values, grid, block, dynamic LDS) and launches from the plan,
+// pick() turning the selectors into template arguments. Which combinations exist is decided by the
+// constexpr *_has predicates alone: the plan calls them at run time, the launcher in `if constexpr`, so a
+// kernel is instantiated exactly when a plan can name it. Whoever else needs a launch's grid (the L2
+// warm-up descriptor, the experiment launches at the end) reads the plan.
+
 // 256 x 256-tile prefill GEMM (gemm_pf.hip) where it fills the chip
-bool zk_gemm_pf_applies(int M, int N, int K, int nsplit);
+bool zk_gemm_pf_applies(int M, int N, int K, int nsplit, int mode, long* tiles, int* block, int* lds);
 int zk_gemm_pf(const void* A, long lda, const void* W, int M, int N, int K, int mode, float* C, void* Cb,
                const int32_t* skip, void* stream);
 
-// k_gemm_ws compute waves per workgroup for this GEMM: 4 (64 columns), or for the slab GEMMs whose
-// 64-column grid fits the 256 CUs badly ZK_WS_NARROW (fewer than ZK_WS_NARROW_BELOW workgroups: more,
-// narrower ones) or ZK_WS_WIDE (more than 256: fewer, wider ones, so no CU runs two)
-static int ws_ncw(int M, int N, int nsplit, int mode) {
-    if (ZK_WS_NCW != 4 || mode != 0 || M <= 64) return ZK_WS_NCW;
+namespace {
+
+// pick(f, v1, Ints<...>{}, v2, Ints<...>{}, ...) calls f(std::integral_constant<int, V1>{}, ...) for the
+// listed constants equal to the run-time values v1, v2, ...; false when a value is not listed
+template <int... Vs> struct Ints {};
+template <class F> bool pick(F&& f) { return f(), true; }
+template <class F, int... Vs, class... More>
+bool pick(F&& f, int v, Ints<Vs...>, More... more) {
+    return ((v == Vs && pick([&](auto... rest) { f(std::integral_constant<int, Vs>{}, rest...); }, more...)) || ...);
+}
+constexpr bool one_of(int v, std::initializer_list<int> list) {
+    for (int x : list)
+        if (x == v) return true;
+    return false;
+}
+
+// k_gemv_rk<mode, 2, ks, pf>: K slices of ks x 128 (ks x 32 per wave), at most 8 k-steps in flight
+constexpr bool rk_has(int mode, int ks) { return mode == 0 ? one_of(ks, {1, 2, 4, 8, 16}) : one_of(ks, {4, 8, 16}); }
+constexpr int rk_pf(int ks) { return ks < 8 ? ks : 8; }
+
+// k_gemm_ws<mode, nchunks, PF, mt, ncw>. Its M <= 16 form (mt = 1) is reached only by a K slice
+// k_gemv_rk has no form for -- the two lists hold the same slices, so that is mode 1 at 4 chunks alone --
+// and workgroups of other than ZK_WS_NCW compute waves only by the 128-row slab GEMMs (ws_ncw).
+static_assert(ZK_WS_NARROW == 0 || ZK_WS_NARROW == 2 || ZK_WS_NARROW == 3, "ZK_WS_NARROW: 2 or 3 (0: off)");
+constexpr bool ws_ncw_varies(int mode, int mt) { return ZK_WS_NCW == 4 && mode == 0 && mt == 8; }
+constexpr bool ws_has(int mode, int nchunks, int mt, int ncw) {
+    if (!(mode == 0 ? one_of(nchunks, {2, 4, 8, 16, 32}) : one_of(nchunks, {4, 8, 16, 32}))) return false;
+    if (mt == 1 && nchunks % 2 == 0 && rk_has(mode, nchunks / 2)) return false;
+    if (ncw == ZK_WS_NCW) return true;
+    return ws_ncw_varies(mode, mt) &&
+           ((ZK_WS_NARROW > 0 && ncw >= ZK_WS_NARROW && ncw <= 3) || (ZK_WS_WIDE > 0 && ncw == ZK_WS_WIDE));
+}
+// k_gemm_ws compute waves per workgroup: 4 (64 columns), or for the slab GEMMs whose 64-column grid fits
+// the 256 CUs badly ZK_WS_NARROW.. 3 (fewer than ZK_WS_NARROW_BELOW workgroups -- the c5 Mamba in_proj,
+// N = 8512 unsplit: 133; the c3 out_proj, split 4: 128 -- run more, narrower ones, the most that still fit
+// one per CU: the in_proj at 2 waves would be 266 workgroups, c5 decode 4.34 -> 4.64 ms) or ZK_WS_WIDE
+// (more than 256: fewer, wider ones, so no CU runs two). The same per-column K order: bit-identical results.
+int ws_ncw(int mt, int N, int nsplit, int mode) {
+    if (!ws_ncw_varies(mode, mt)) return ZK_WS_NCW;
     auto tiles = [&](int nw) { return (long)((N + 16 * nw - 1) / (16 * nw)) * nsplit; };
     if (ZK_WS_NARROW > 0 && tiles(4) < ZK_WS_NARROW_BELOW)
         for (int nw = ZK_WS_NARROW; nw <= 3; ++nw)          // the largest grid that still fits the CUs
@@ -1073,32 +1133,132 @@ static int ws_ncw(int M, int N, int nsplit, int mode) {
     return 4;
 }
 
-ZkWarm zk_gemm_warm_desc(const void* W, int M, int N, int K, int nsplit, int mode, int chunks) {
-    if (W == nullptr || M <= 16 || ZK_WS_NCW != 4 || !ws_regime(M, K, nsplit) || K % (nsplit * BK) != 0)
-        return ZkWarm{nullptr, 0, 0, 0, 0};
-    const int nw = ws_ncw(M, N, nsplit, mode);
-    const int gx = (N + 16 * nw - 1) / (16 * nw);
-    const int excess = gx * nw - (N + 15) / 16;                 // grid tiles wholly past N (< nw)
-    return ZkWarm{W, K, gx, nsplit, std::min(chunks, K / nsplit / BK) | (nw != 4 ? nw << 16 : 0) | (excess << 24)};
+// k_gemm<mode, u, ntw>: two 16-column tiles per wave for the slab GEMMs (c3 prefill: in_proj 1.01 vs
+// 1.09 ms, fc2 1.98 vs 2.29 ms; the SwiGLU fc1 is faster with one: 4.87 vs 5.24 ms)
+constexpr bool tile_has(int mode, int u, int ntw) { return one_of(u, {1, 2, 4}) && (ntw == 1 || (ntw == 2 && !mode)); }
+
+enum GemmFamily { GEMM_RK, GEMM_WS, GEMM_PF, GEMM_TILE };
+struct GemmPlan {
+    GemmFamily family;
+    int mode;
+    int ks, pf;               // GEMM_RK: k_gemv_rk<mode, 2, ks, pf>
+    int nchunks, mt, ncw;     // GEMM_WS: k_gemm_ws<mode, nchunks, WS_PF / WS_PF0, mt, ncw>
+    int ws_gx;                // ... and its column grid. The four are set in the whole decode regime (M <= 128, at
+                              // most 32 chunks; ws_gx = 0 outside it), also for a slice that falls through to k_gemm
+    int u, ntw;               // GEMM_TILE: k_gemm<mode, u, ntw>
+    long gx;                  // grid gx x gy x gz, threads per workgroup
+    int gy, gz, block;
+    size_t lds;               // dynamic LDS, before k_gemm_ws's 1 KB warm-up sink
+};
+
+// The launch of zk_gemm_bf16(M, N, K, nsplit, mode), arguments already validated. The families in order;
+// a shape a family has no instantiation for falls through to the next one.
+GemmPlan gemm_plan(int M, int N, int K, int nsplit, int mode) {
+    const int kslice = K / nsplit, nchunks = kslice / BK;
+    GemmPlan p{};
+    p.mode = mode, p.gy = 1, p.gz = nsplit;
+    // weight-stream GEMV (B <= 8 decode): 2 column tiles per workgroup, K quarters per wave
+    if (M <= 16 && kslice % 128 == 0 && rk_has(mode, kslice / 128)) {
+        p.family = GEMM_RK, p.ks = kslice / 128, p.pf = rk_pf(p.ks);
+        p.gx = (N + 31) / 32, p.block = 256;
+        return p;
+    }
+    // decode: the loader-wave GEMM, every row of the batch in one workgroup
+    if (M <= BM && nchunks <= 32) {
+        const int mt = M <= 16 ? 1 : (M <= 32 ? 2 : (M <= 64 ? 4 : 8)), ncw = ws_ncw(mt, N, nsplit, mode);
+        p.nchunks = nchunks, p.mt = mt, p.ncw = ncw, p.ws_gx = (N + 16 * ncw - 1) / (16 * ncw);
+        if (ws_has(mode, nchunks, mt, ncw)) {
+            p.family = GEMM_WS, p.gx = p.ws_gx, p.block = 64 * (ncw + ws_nld(ncw, mt));
+            p.lds = (size_t)WS_NB * mt * 16 * BK * 2;
+            return p;
+        }
+    }
+    // large M (prefill) with at least one 256 x 256 tile per CU: gemm_pf.hip
+    int pf_lds = 0;
+    if (zk_gemm_pf_applies(M, N, K, nsplit, mode, &p.gx, &p.block, &pf_lds)) {
+        p.family = GEMM_PF, p.lds = pf_lds;
+        return p;
+    }
+    // everything else: prefill below that size, K slices the decode kernels have no form for
+    p.family = GEMM_TILE, p.u = nchunks % 4 == 0 ? 4 : (nchunks % 2 == 0 ? 2 : 1);
+    p.ntw = (tile_has(mode, p.u, 2) && M > BM && N >= 8 * BN) ? 2 : 1;
+    p.gx = (N + BN * p.ntw - 1) / (BN * p.ntw), p.gy = (M + BM - 1) / BM, p.block = NT;
+    return p;
 }
 
-// Host mirror of warm_unit's tile bound for the descriptor zk_gemm_warm_desc builds: the number of
-// 16-column tiles of the packed image the warm-up of this GEMM reads (0 when it is off). Tests check
-// it against ceil(N / 16), the tiles the packed image holds a column of (the 48-column
-// grid of the c5 Mamba in_proj once warmed 2 tiles past the image).
-extern "C" int zk_gemm_warm_tiles(int M, int N, int K, int nsplit, int mode, int chunks) {
-    static const char dummy = 0;
-    const ZkWarm d = zk_gemm_warm_desc(&dummy, M, N, K, nsplit, mode, chunks);
-    if (d.W == nullptr) return 0;
-    const int ng = std::max(1, (d.chunks >> 8) & 255), nw = ((d.chunks >> 16) & 255) ? ((d.chunks >> 16) & 255) : 4;
-    int hi = 0;
-    for (int bx = 0; bx < d.gx; ++bx)
-        for (int w = 0; w < nw; ++w)
-            for (int g = 0; g < ng; ++g) {
-                const int tile = (bx * nw + w) * ng + g;
-                if (tile < d.gx * nw * ng - ((d.chunks >> 24) & 255)) hi = std::max(hi, tile + 1);
+int gemm_launch(const GemmPlan& p, const void* A, long lda, const void* W, int M, int N, int K, int nsplit,
+                float* Cpart, void* Cout, const int32_t* skip_flag, ZkWarm warm, hipStream_t stream) {
+    if (p.family == GEMM_PF) return zk_gemm_pf(A, lda, W, M, N, K, p.mode, Cpart, Cout, skip_flag, stream);
+    bool launched = false;
+    auto launch = [&](auto kern, size_t lds, auto... more) {
+        hipLaunchKernelGGL(kern, dim3((unsigned)p.gx, p.gy, p.gz), dim3(p.block), lds, stream, (const bf16_t*)A, lda,
+                           (const bf16_t*)W, M, N, K, K / nsplit, Cpart, (bf16_t*)Cout, skip_flag, more...);
+        launched = true;
+    };
+    if (p.family == GEMM_RK)
+        pick([&](auto mode, auto ks) {
+            if constexpr (rk_has(mode(), ks())) launch(&k_gemv_rk<mode(), 2, ks(), rk_pf(ks())>, 0);
+        }, p.mode, Ints<0, 1>{}, p.ks, Ints<1, 2, 4, 8, 16>{});
+    else if (p.family == GEMM_WS)
+        pick([&](auto mode, auto nch, auto mt, auto ncw) {
+            if constexpr (ws_has(mode(), nch(), mt(), ncw())) {
+                auto kern = &k_gemm_ws<mode(), nch(), (mode() ? WS_PF : WS_PF0), mt(), ncw()>;
+                const size_t lds = p.lds + (warm.W ? 1024 : 0);     // + warm-up sink
+                if (lds > 65536)
+                    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
+                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                launch(kern, lds, (const bf16_t*)warm.W, warm.K, warm.gx, warm.gz, warm.chunks);
             }
-    return hi;
+        }, p.mode, Ints<0, 1>{}, p.nchunks, Ints<2, 4, 8, 16, 32>{}, p.mt, Ints<1, 2, 4, 8>{}, p.ncw,
+             Ints<2, 3, (ZK_WS_WIDE > 0 ? ZK_WS_WIDE : ZK_WS_NCW), ZK_WS_NCW>{});
+    else
+        pick([&](auto mode, auto u, auto ntw) {
+            if constexpr (tile_has(mode(), u(), ntw())) launch(&k_gemm<mode(), u(), ntw()>, 0);
+        }, p.mode, Ints<0, 1>{}, p.u, Ints<1, 2, 4>{}, p.ntw, Ints<1, 2>{});
+    ZK_REQUIRE(launched, "zk_gemm_bf16: no kernel for the plan (family %d)", (int)p.family);
+    ZK_CHECK_LAUNCH("zk_gemm_bf16");
+    return 0;
+}
+
+// k_gemv_f layouts: 0 half a tile per workgroup, 1 one tile, 2 two tiles. The template selectors of a
+// launch follow from (layout, LayerNorm prologue, KSW = K / 32 k-steps of the workgroup, XR rows).
+struct GfForm { int ntw; bool half; int nw, ks, pf; };
+constexpr bool operator==(const GfForm& a, const GfForm& b) {
+    return a.ntw == b.ntw && a.half == b.half && a.nw == b.nw && a.ks == b.ks && a.pf == b.pf;
+}
+constexpr GfForm gf_form(int lay, bool ln, int ksw, int xr) {
+    const bool half = lay == 0;
+    const int nw = half ? ZK_GF_NWH : ZK_GF_NW, ks = ksw / nw, nl = half ? ks / 2 : ks;
+    const int pb = (xr == 2 && ln && lay == 1) ? ZK_GF_PFLN : ZK_GF_PF;
+    return GfForm{lay == 2 ? 2 : 1, half, nw, ks, nl < pb ? nl : pb};
+}
+constexpr int gf_grid(int lay, int tiles) { return lay == 0 ? 2 * tiles : (lay == 2 ? (tiles + 1) / 2 : tiles); }
+// half tiles need a plain or residual epilogue and no LayerNorm prologue; the prologue needs K = 2048
+constexpr bool gf_has(int mode, bool ln, int lay, int ksw) {
+    return (lay != 0 || (mode != 1 && !ln)) && (ln ? ksw == 64 : one_of(ksw, {64, 128, 256}));
+}
+
+struct GemvPlan { int lay, ksw, xr, grid, block; };      // k_gemv_f<mode, ln, gf_form(lay, ln, ksw, xr)..., 0, xr>
+// >= 256 workgroups: half tiles below 256 tiles (out_proj / fc2: N = 2048), pairs of tiles
+// from 512 (fc1, heads). With the LayerNorm prologue one tile per workgroup even below 256
+// tiles (in_proj, N = 3072: 192 workgroups, 6.5 vs 7.5 us with half tiles at B = 1 --
+// the prologue's latency, not the weight stream, sets its time; tools/gemv_probe.sh)
+GemvPlan gemv_plan(int M, int N, int K, int mode, bool ln) {
+    const int tiles = (N + 15) / 16, ksw = K / 32, xr = M <= 2 ? 2 : 16;
+    const int lay = (gf_has(mode, ln, 0, ksw) && tiles < 256) ? 0 : (tiles >= 512 ? 2 : 1);
+    return GemvPlan{lay, ksw, xr, gf_grid(lay, tiles), 64 * gf_form(lay, ln, ksw, xr).nw};
+}
+
+}  // namespace
+
+int zk_gemm_bf16_warm(const void* A, long lda, const void* W, int M, int N, int K, int nsplit, int mode,
+                      float* Cpart, void* Cout, const int32_t* skip_flag, ZkWarm warm, void* stream) {
+    ZK_REQUIRE(M > 0 && N > 0 && K > 0, "zk_gemm_bf16: empty shape M=%d N=%d K=%d", M, N, K);
+    ZK_REQUIRE(nsplit >= 1 && K % (nsplit * BK) == 0, "zk_gemm_bf16: K=%d must be a multiple of nsplit*%d", K, BK);
+    ZK_REQUIRE(lda >= K && lda % 8 == 0, "zk_gemm_bf16: lda=%ld", lda);
+    ZK_REQUIRE(mode == 0 || (mode == 1 && nsplit == 1 && N % 16 == 0), "zk_gemm_bf16: bad mode/nsplit");
+    return gemm_launch(gemm_plan(M, N, K, nsplit, mode), A, lda, W, M, N, K, nsplit, Cpart, Cout, skip_flag, warm,
+                       (hipStream_t)stream);
 }
 
 extern "C" int zk_gemm_bf16(const void* A, long lda, const void* W, int M, int N, int K, int nsplit, int mode,
@@ -1107,142 +1267,31 @@ extern "C" int zk_gemm_bf16(const void* A, long lda, const void* W, int M, int N
                              stream);
 }
 
-int zk_gemm_bf16_warm(const void* A, long lda, const void* W, int M, int N, int K, int nsplit, int mode,
-                      float* Cpart, void* Cout, const int32_t* skip_flag, ZkWarm warm, void* stream) {
-    ZK_REQUIRE(M > 0 && N > 0 && K > 0, "zk_gemm_bf16: empty shape M=%d N=%d K=%d", M, N, K);
-    ZK_REQUIRE(nsplit >= 1 && K % (nsplit * BK) == 0, "zk_gemm_bf16: K=%d must be a multiple of nsplit*%d", K, BK);
-    ZK_REQUIRE(lda >= K && lda % 8 == 0, "zk_gemm_bf16: lda=%ld", lda);
-    ZK_REQUIRE(mode == 0 || (mode == 1 && nsplit == 1 && N % 16 == 0), "zk_gemm_bf16: bad mode/nsplit");
-    const int nchunks = K / nsplit / BK;
-    if (M <= 16 && (K / nsplit) % 128 == 0) {
-        // weight-stream GEMV (B <= 8 decode): 2 column tiles per workgroup, K quarters per wave
-        const int ks = K / nsplit / 128;
-        dim3 g((N + 31) / 32, 1, nsplit);
-        bool handled = false;
-#define ZK_GV(MODE_, KS_)                                                                                         \
-    do {                                                                                                          \
-        constexpr int PF_ = KS_ < 8 ? KS_ : 8;                                                                    \
-        hipLaunchKernelGGL((k_gemv_rk<MODE_, 2, KS_, PF_>), g, dim3(256), 0, (hipStream_t)stream,                 \
-                           (const bf16_t*)A, lda, (const bf16_t*)W, M, N, K, K / nsplit, Cpart, (bf16_t*)Cout,     \
-                           skip_flag);                                                                             \
-        handled = true;                                                                                           \
-    } while (0)
-        if (mode == 0) {
-            switch (ks) {
-                case 1: ZK_GV(0, 1); break;
-                case 2: ZK_GV(0, 2); break;
-                case 4: ZK_GV(0, 4); break;
-                case 8: ZK_GV(0, 8); break;
-                case 16: ZK_GV(0, 16); break;
-                default: break;
-            }
-        } else {
-            switch (ks) {
-                case 4: ZK_GV(1, 4); break;
-                case 8: ZK_GV(1, 8); break;
-                case 16: ZK_GV(1, 16); break;
-                default: break;
-            }
-        }
-#undef ZK_GV
-        if (handled) {
-            ZK_CHECK_LAUNCH("zk_gemm_bf16");
-            return 0;
-        }
-    }
-    if (M <= BM && nchunks <= 32) {
-        constexpr int NCW = ZK_WS_NCW;            // compute waves per workgroup
-        // a slab GEMM whose 64-column tiles x splits leave a quarter of the CUs idle (the c5 Mamba
-        // in_proj: N = 8512 unsplit, 133 tiles; the c3 out_proj, split 4: 128) runs narrower
-        // workgroups of 2 or 3 compute waves (16 columns each), the most that still fit one
-        // workgroup per CU (the Mamba in_proj at 2 waves would be 266 workgroups for 256 CUs:
-        // c5 decode 4.34 -> 4.64 ms); the same per-column K order (bit-identical results).
-        const int ncw = M > 16 ? ws_ncw(M, N, nsplit, mode) : NCW;
-        dim3 g((N + 16 * ncw - 1) / (16 * ncw), 1, nsplit);
-        const int MT = M <= 16 ? 1 : (M <= 32 ? 2 : (M <= 64 ? 4 : 8));
-        const size_t lds = (size_t)WS_NB * MT * 16 * BK * 2 + (warm.W ? 1024 : 0);     // + warm-up sink
-#define ZK_WS_LAUNCH4(MODE_, NCH_, MT_, NCW_)                                                                      \
-    do {                                                                                                          \
-        auto kern_ = &k_gemm_ws<MODE_, NCH_, (MODE_ ? WS_PF : WS_PF0), MT_, NCW_>;                                 \
-        if (lds > 65536)                                                                                          \
-            hipFuncSetAttribute(reinterpret_cast<const void*>(kern_), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                (int)lds);                                                                        \
-        hipLaunchKernelGGL(kern_, g, dim3(64 * (NCW_ + ws_nld<NCW_, MT_>())), lds, (hipStream_t)stream,                \
-                           (const bf16_t*)A, lda, (const bf16_t*)W, M, N, K, K / nsplit, Cpart, (bf16_t*)Cout,      \
-                           skip_flag, (const bf16_t*)warm.W, warm.K, warm.gx, warm.gz, warm.chunks);              \
-        handled = true;                                                                                           \
-    } while (0)
-#define ZK_WS_LAUNCH3(MODE_, NCH_, MT_)                                                                            \
-    do {                                                                                                          \
-        if ((MODE_) == 0 && (MT_) == 8 && ncw == 2 && NCW == 4) ZK_WS_LAUNCH4(MODE_, NCH_, MT_, 2);               \
-        else if ((MODE_) == 0 && (MT_) == 8 && ncw == 3 && NCW == 4) ZK_WS_LAUNCH4(MODE_, NCH_, MT_, 3);          \
-        else if ((MODE_) == 0 && (MT_) == 8 && ncw == ZK_WS_WIDE_W && ncw != NCW)                                   \
-            ZK_WS_LAUNCH4(MODE_, NCH_, MT_, ZK_WS_WIDE_W);                                                         \
-        else ZK_WS_LAUNCH4(MODE_, NCH_, MT_, NCW);                                                                \
-    } while (0)
-#define ZK_WS_LAUNCH(MODE_, NCH_)                                                                                  \
-    do {                                                                                                          \
-        switch (MT) {                                                                                             \
-            case 1: ZK_WS_LAUNCH3(MODE_, NCH_, 1); break;                                                         \
-            case 2: ZK_WS_LAUNCH3(MODE_, NCH_, 2); break;                                                         \
-            case 4: ZK_WS_LAUNCH3(MODE_, NCH_, 4); break;                                                         \
-            default: ZK_WS_LAUNCH3(MODE_, NCH_, 8); break;                                                        \
-        }                                                                                                         \
-    } while (0)
-        bool handled = false;
-        if (mode == 0) {
-            switch (nchunks) {
-                case 2: ZK_WS_LAUNCH(0, 2); break;
-                case 4: ZK_WS_LAUNCH(0, 4); break;
-                case 8: ZK_WS_LAUNCH(0, 8); break;
-                case 16: ZK_WS_LAUNCH(0, 16); break;
-                case 32: ZK_WS_LAUNCH(0, 32); break;
-                default: break;
-            }
-        } else {
-            switch (nchunks) {
-                case 4: ZK_WS_LAUNCH(1, 4); break;
-                case 8: ZK_WS_LAUNCH(1, 8); break;
-                case 16: ZK_WS_LAUNCH(1, 16); break;
-                case 32: ZK_WS_LAUNCH(1, 32); break;
-                default: break;
-            }
-        }
-        if (handled) {
-            ZK_CHECK_LAUNCH("zk_gemm_bf16");
-            return 0;
-        }
-#undef ZK_WS_LAUNCH4
-#undef ZK_WS_LAUNCH3
-#undef ZK_WS_LAUNCH
-    }
-    // large M (prefill) with at least one 256 x 256 tile per CU: gemm_pf.hip
-    if (zk_gemm_pf_applies(M, N, K, nsplit))
-        return zk_gemm_pf(A, lda, W, M, N, K, mode, Cpart, Cout, skip_flag, stream);
-    // large M (prefill): two 16-column tiles per wave for the slab GEMMs (c3 prefill: in_proj
-    // 1.01 vs 1.09 ms, fc2 1.98 vs 2.29 ms; the SwiGLU fc1 is faster with one: 4.87 vs 5.24 ms)
-    const int ntw = (mode == 0 && M > BM && N >= 8 * BN) ? 2 : 1;
-    dim3 grid((N + BN * ntw - 1) / (BN * ntw), (M + BM - 1) / BM, nsplit);
-    const int U = (nchunks % 4 == 0) ? 4 : (nchunks % 2 == 0 ? 2 : 1);
-#define ZK_GEMM_LAUNCH(MODE_, U_)                                                                         \
-    do {                                                                                                  \
-        if (ntw == 2)                                                                                     \
-            hipLaunchKernelGGL((k_gemm<MODE_, U_, 2>)       , grid, dim3(NT), 0, (hipStream_t)stream,     \
-                               (const bf16_t*)A, lda, (const bf16_t*)W, M, N, K, K / nsplit, Cpart,       \
-                               (bf16_t*)Cout, skip_flag);                                                 \
-        else                                                                                              \
-            hipLaunchKernelGGL((k_gemm<MODE_, U_>), grid, dim3(NT), 0, (hipStream_t)stream,               \
-                               (const bf16_t*)A, lda, (const bf16_t*)W, M, N, K, K / nsplit, Cpart,       \
-                               (bf16_t*)Cout, skip_flag);                                                 \
-    } while (0)
-    if (mode == 0) {
-        if (U == 4) ZK_GEMM_LAUNCH(0, 4); else if (U == 2) ZK_GEMM_LAUNCH(0, 2); else ZK_GEMM_LAUNCH(0, 1);
-    } else {
-        if (U == 4) ZK_GEMM_LAUNCH(1, 4); else if (U == 2) ZK_GEMM_LAUNCH(1, 2); else ZK_GEMM_LAUNCH(1, 1);
-    }
-#undef ZK_GEMM_LAUNCH
-    ZK_CHECK_LAUNCH("zk_gemm_bf16");
-    return 0;
+// The warm-up descriptor (warm.h) of a GEMM of the decode regime with M > 16: k_gemm_ws's grid from the plan.
+// (As it always has, it also describes that grid for a slice k_gemm_ws has no instantiation for -- 1, 3 or 5
+// chunks; 2 in mode 1 -- which k_gemm runs: the warm-up then still reads that GEMM's first weight chunks.)
+ZkWarm zk_gemm_warm_desc(const void* W, int M, int N, int K, int nsplit, int mode, int chunks) {
+    const ZkWarm off{nullptr, 0, 0, 0, 0};
+    if (W == nullptr || M <= 16 || ZK_WS_NCW != 4 || nsplit < 1 || K % (nsplit * BK) != 0) return off;
+    const GemmPlan p = gemm_plan(M, N, K, nsplit, mode);
+    if (p.ws_gx == 0) return off;
+    const int excess = p.ws_gx * p.ncw - (N + 15) / 16;         // grid tiles wholly past N (< ncw)
+    return ZkWarm{W, K, p.ws_gx, p.gz, warm_pack(std::min(chunks, p.nchunks), 1, p.ncw, excess)};
+}
+
+// The number of 16-column tiles of the packed image the warm-up of this GEMM reads (0 when it is off), by
+// warm_unit's own tile numbering and bound (warm.h). Tests check it against ceil(N / 16), the tiles the
+// image holds a column of (the 48-column grid of the c5 Mamba in_proj once warmed 2 tiles past it).
+extern "C" int zk_gemm_warm_tiles(int M, int N, int K, int nsplit, int mode, int chunks) {
+    static const char dummy = 0;
+    const ZkWarm d = zk_gemm_warm_desc(&dummy, M, N, K, nsplit, mode, chunks);
+    int hi = 0;
+    for (int bx = 0; d.W != nullptr && bx < d.gx; ++bx)
+        for (int w = 0; w < warm_nw(d.chunks); ++w)
+            for (int g = 0; g < warm_ng(d.chunks); ++g)
+                if (warm_tile(d.chunks, bx, w, g) < warm_ntiles(d.chunks, d.gx))
+                    hi = std::max(hi, warm_tile(d.chunks, bx, w, g) + 1);
+    return hi;
 }
 
 extern "C" int zk_gemv_fused(const void* A, long lda, const void* W, int M, int N, int K, int mode,
@@ -1256,75 +1305,82 @@ extern "C" int zk_gemv_fused(const void* A, long lda, const void* W, int M, int 
     ZK_REQUIRE((ln_w == nullptr) == (ln_b == nullptr), "zk_gemv_fused: LN needs both w and b");
     ZK_REQUIRE(ln_w == nullptr || K == 2048, "zk_gemv_fused: LN prologue needs K = 2048 (K=%d)", K);
     ZK_REQUIRE(mode == 0 ? Cf != nullptr : Cb != nullptr, "zk_gemv_fused: missing output");
-    const int tiles = (N + 15) / 16;
-    // >= 256 workgroups: half tiles below 256 tiles (out_proj / fc2: N = 2048), pairs of tiles
-    // from 512 (fc1, heads). With the LayerNorm prologue one tile per workgroup even below 256
-    // tiles (in_proj, N = 3072: 192 workgroups, 6.5 vs 7.5 us with half tiles at B = 1 --
-    // the prologue's latency, not the weight stream, sets its time; tools/gemv_probe.sh)
-    int lay = (mode != 1 && tiles < 256 && !ln_w) ? 0 : (tiles >= 512 ? 2 : 1);
-    const int grid = lay == 0 ? 2 * tiles : (lay == 2 ? (tiles + 1) / 2 : tiles);
-    const bool ln = ln_w != nullptr;
-    (void)ln;
-    bool handled = false;
-    // tuning knobs (compile-time, build_variant): waves per workgroup, k-steps in flight per wave
-#ifndef ZK_GF_NW
-#define ZK_GF_NW 4
-#endif
-#ifndef ZK_GF_NWH
-#define ZK_GF_NWH 8
-#endif
-#ifndef ZK_GF_PF
-#define ZK_GF_PF 8
-#endif
-#ifndef ZK_GF_PFLN
-#define ZK_GF_PFLN 12              // k-steps in flight of the B = 1 LayerNorm-prologue one-tile GEMV (in_proj):
-#endif                             // c2 step 1.045-1.048 vs 1.051-1.053 ms at 8, 1.054-1.055 at 16 (r3_b1_gemv_pf_ab)
-#define ZK_GF(MODE_, LN_, NTW_, HALF_, NW_, KSW_)                                                            \
-    do {                                                                                                      \
-        constexpr int KS_ = (KSW_) / (NW_);                                                                   \
-        constexpr int NL_ = HALF_ ? KS_ / 2 : KS_;                                                            \
-        constexpr int PB_ = (LN_ && NTW_ == 1 && !HALF_) ? ZK_GF_PFLN : ZK_GF_PF;                           \
-        if (M <= 2)                                                                               \
-            hipLaunchKernelGGL((k_gemv_f<MODE_, LN_, NTW_, HALF_, NW_, KS_, (NL_ < PB_ ? NL_ : PB_),              \
-                                          0, 2>),                                                             \
-                               dim3(grid), dim3(64 * (NW_)), 0, (hipStream_t)stream, (const bf16_t*)A, lda,    \
-                               (const bf16_t*)W, M, N, K, (const bf16_t*)ln_w, (const bf16_t*)ln_b, eps, Cf,    \
-                               (bf16_t*)Cb, skip_flag, nullptr, 1);                                            \
-        else                                                                                                  \
-            hipLaunchKernelGGL((k_gemv_f<MODE_, LN_, NTW_, HALF_, NW_, KS_, (NL_ < ZK_GF_PF ? NL_ : ZK_GF_PF)>),  \
-                               dim3(grid), dim3(64 * (NW_)), 0, (hipStream_t)stream, (const bf16_t*)A, lda,    \
-                               (const bf16_t*)W, M, N, K, (const bf16_t*)ln_w, (const bf16_t*)ln_b, eps, Cf,    \
-                               (bf16_t*)Cb, skip_flag, nullptr, 1);                                            \
-        handled = true;                                                                                       \
-    } while (0)
-#define ZK_GF_LAY(MODE_, LN_, KSW_)                                     \
-    do {                                                                \
-        if (lay == 0) ZK_GF(MODE_, LN_, 1, true, ZK_GF_NWH, KSW_);      \
-        else if (lay == 1) ZK_GF(MODE_, LN_, 1, false, ZK_GF_NW, KSW_); \
-        else ZK_GF(MODE_, LN_, 2, false, ZK_GF_NW, KSW_);               \
-    } while (0)
-#define ZK_GF_MODE(LN_, KSW_)                       \
-    do {                                            \
-        if (mode == 0) ZK_GF_LAY(0, LN_, KSW_);     \
-        else if (mode == 1) ZK_GF_LAY(1, LN_, KSW_); \
-        else ZK_GF_LAY(2, LN_, KSW_);               \
-    } while (0)
-    // KSW = K / 32: k-steps of the whole workgroup
-    if (ln) ZK_GF_MODE(true, 64);
-    else if (K == 2048) ZK_GF_MODE(false, 64);
-    else if (K == 4096) ZK_GF_MODE(false, 128);
-    else ZK_GF_MODE(false, 256);
-#undef ZK_GF_MODE
-#undef ZK_GF_LAY
-#undef ZK_GF
-    ZK_REQUIRE(handled, "zk_gemv_fused: no kernel for K=%d", K);
+    const GemvPlan p = gemv_plan(M, N, K, mode, ln_w != nullptr);
+    bool launched = false;
+    pick([&](auto mode_, auto ln, auto lay, auto ksw, auto xr) {
+        if constexpr (gf_has(mode_(), ln() != 0, lay(), ksw())) {
+            constexpr GfForm F = gf_form(lay(), ln() != 0, ksw(), xr());
+            hipLaunchKernelGGL((k_gemv_f<mode_(), ln() != 0, F.ntw, F.half, F.nw, F.ks, F.pf, 0, xr()>), dim3(p.grid),
+                               dim3(p.block), 0, (hipStream_t)stream, (const bf16_t*)A, lda, (const bf16_t*)W, M, N, K,
+                               (const bf16_t*)ln_w, (const bf16_t*)ln_b, eps, Cf, (bf16_t*)Cb, skip_flag, nullptr, 1);
+            launched = true;
+        }
+    }, mode, Ints<0, 1, 2>{}, ln_w != nullptr, Ints<0, 1>{}, p.lay, Ints<0, 1, 2>{}, p.ksw, Ints<64, 128, 256>{}, p.xr,
+         Ints<2, 16>{});
+    ZK_REQUIRE(launched, "zk_gemv_fused: no kernel for K=%d", K);
     ZK_CHECK_LAUNCH("zk_gemv_fused");
     return 0;
 }
 
-// Experiment (tools/microbench.py gemv_warm): a launch that pre-reads into each XCD's L2 the first
-// `steps` weight loads of every wave of a k_gemv_f launch of the given layout (same grid, same
-// workgroup -> tile / K-range map and per-lane addresses), by LDS-DMA into a sink.
+#ifdef ZK_GF_PROF
+extern "C" int zk_gf_prof_set(uint64_t* p) {
+    return hipMemcpyToSymbol(HIP_SYMBOL(g_gf_prof), &p, sizeof(p)) == hipSuccess ? 0 : -1;
+}
+#endif
+
+extern "C" int zk_gemv_qkv_rope(const void* x, const void* W, int M, int H, int Hkv, int hd, const void* ln_w,
+                                const void* ln_b, float eps, void* q_out, void* k_cache, void* vt_cache, int Smax,
+                                const int32_t* pos_dev, const float* freqs, const int32_t* skip_flag, void* stream) {
+    ZK_REQUIRE(M >= 1 && M <= 2, "zk_gemv_qkv_rope: M=%d (1..2)", M);
+    ZK_REQUIRE(hd == 128 && H % Hkv == 0 && H / Hkv <= AT_G, "zk_gemv_qkv_rope: H=%d Hkv=%d hd=%d", H, Hkv, hd);
+    const int K = H * hd, N = (H + 2 * Hkv) * hd;
+    ZK_REQUIRE(K == 2048, "zk_gemv_qkv_rope: d_model %d (2048 only: the LayerNorm prologue)", K);
+    ZK_REQUIRE(x && W && ln_w && ln_b && q_out && k_cache && vt_cache && pos_dev && freqs,
+               "zk_gemv_qkv_rope: null argument");
+    ZK_REQUIRE(Smax > 0 && Smax % 32 == 0, "zk_gemv_qkv_rope: Smax=%d", Smax);
+    const GfQkv qk{(bf16_t*)k_cache, (bf16_t*)vt_cache, pos_dev, freqs, H, Hkv, Smax};
+    // the epilogue rotates column pairs inside one whole tile: the one-tile layout, which the plan gives
+    // every N this entry accepts (at most 48 heads of 128 columns: 384 tiles, with the LayerNorm prologue)
+    const GemvPlan p = gemv_plan(M, N, K, 3, true);
+    ZK_REQUIRE(p.lay == 1 && p.xr == 2, "zk_gemv_qkv_rope: N=%d is not a one-tile GEMV", N);
+    constexpr GfForm F = gf_form(1, true, 64, 2);
+    hipLaunchKernelGGL((k_gemv_f<3, true, F.ntw, F.half, F.nw, F.ks, F.pf, 0, 2>), dim3(p.grid), dim3(p.block), 0,
+                       (hipStream_t)stream, (const bf16_t*)x, (long)K, (const bf16_t*)W, M, N, K,
+                       (const bf16_t*)ln_w, (const bf16_t*)ln_b, eps, nullptr, (bf16_t*)q_out, skip_flag, nullptr, 1,
+                       qk);
+    ZK_CHECK_LAUNCH("zk_gemv_qkv_rope");
+    return 0;
+}
+
+extern "C" int zk_gemv_attn_out(const float* work, int nsplit, int Hkv, const void* W, int M, int N, int K,
+                                void* x, const int32_t* skip_flag, void* stream) {
+    ZK_REQUIRE(M >= 1 && M <= 2, "zk_gemv_attn_out: M=%d (1..2)", M);
+    ZK_REQUIRE(K == 2048 && N > 0 && N % 16 == 0, "zk_gemv_attn_out: K=%d (2048) N=%d", K, N);
+    ZK_REQUIRE(Hkv >= 1 && (K / 128) % Hkv == 0 && (K / 128) / Hkv <= GF_AT_G, "zk_gemv_attn_out: Hkv=%d", Hkv);
+    ZK_REQUIRE(work != nullptr && x != nullptr, "zk_gemv_attn_out: null buffer");
+    // The merge prologue needs half tiles and 8 K-range waves, at every N and whatever ZK_GF_NWH / ZK_GF_PF
+    // say: the form of the residual GEMV (zk_gemv_fused mode 2, M <= 2, N < 4096) at the default switches.
+    constexpr GfForm F{1, true, 8, 8, 4};
+    static_assert(ZK_GF_NWH != 8 || ZK_GF_PF < 4 || F == gf_form(0, false, 64, 2), "zk_gemv_attn_out's layout");
+    const bool listed = pick([&](auto ns) {
+        hipLaunchKernelGGL((k_gemv_f<2, false, F.ntw, F.half, F.nw, F.ks, F.pf, ns(), 2>),
+                           dim3(gf_grid(0, (N + 15) / 16)), dim3(64 * F.nw), 0, (hipStream_t)stream,
+                           reinterpret_cast<const bf16_t*>(work), (long)K, (const bf16_t*)W, M, N, K, nullptr, nullptr,
+                           0.f, nullptr, (bf16_t*)x, skip_flag, work, Hkv);
+    }, nsplit, Ints<2, 4, 8, 16>{});
+    ZK_REQUIRE(listed, "zk_gemv_attn_out: nsplit=%d (2, 4, 8 or 16)", nsplit);
+    ZK_CHECK_LAUNCH("zk_gemv_attn_out");
+    return 0;
+}
+
+// ------------------------------------------------------------------ warm-up experiments
+// Two stand-alone launches that tools/microbench.py times (`gemv_warm`, `warm`; DESIGN.md §6 cites the
+// results); the library itself launches neither. Each imitates a launch above and takes that launch's
+// grid and layout from its plan.
+
+// Pre-reads into each XCD's L2 the first `steps` weight loads of every wave of a k_gemv_f launch of the
+// given layout (same grid, same workgroup -> tile / K-range map and per-lane addresses), by LDS-DMA
+// into a sink.
 template <int NTW, bool HALF, int NW>
 __global__ __launch_bounds__(64 * NW) void k_gemv_warm(const bf16_t* __restrict__ W, int N, int K, int steps) {
     __shared__ __attribute__((aligned(16))) char sink[1024];
@@ -1346,75 +1402,22 @@ __global__ __launch_bounds__(64 * NW) void k_gemv_warm(const bf16_t* __restrict_
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
+// (the layout depends on the GEMV's mode and prologue, which this entry is not told: `lay` stays an argument)
 extern "C" int zk_gemv_warm(const void* W, int N, int K, int lay, int steps, void* stream) {
     ZK_REQUIRE(lay >= 0 && lay <= 2 && steps >= 1 && K % 2048 == 0, "zk_gemv_warm: lay %d steps %d K %d", lay, steps,
                K);
-    const int tiles = (N + 15) / 16;
-    if (lay == 0)
-        hipLaunchKernelGGL((k_gemv_warm<1, true, 8>), dim3(2 * tiles), dim3(512), 0, (hipStream_t)stream,
-                           (const bf16_t*)W, N, K, steps);
-    else if (lay == 1)
-        hipLaunchKernelGGL((k_gemv_warm<1, false, 4>), dim3(tiles), dim3(256), 0, (hipStream_t)stream,
-                           (const bf16_t*)W, N, K, steps);
-    else
-        hipLaunchKernelGGL((k_gemv_warm<2, false, 4>), dim3((tiles + 1) / 2), dim3(256), 0, (hipStream_t)stream,
-                           (const bf16_t*)W, N, K, steps);
+    pick([&](auto lay_) {
+        constexpr GfForm F = gf_form(lay_(), false, 64, 16);
+        hipLaunchKernelGGL((k_gemv_warm<F.ntw, F.half, F.nw>), dim3(gf_grid(lay, (N + 15) / 16)), dim3(64 * F.nw), 0,
+                           (hipStream_t)stream, (const bf16_t*)W, N, K, steps);
+    }, lay, Ints<0, 1, 2>{});
     ZK_CHECK_LAUNCH("zk_gemv_warm");
     return 0;
 }
 
-#ifdef ZK_GF_PROF
-extern "C" int zk_gf_prof_set(uint64_t* p) {
-    return hipMemcpyToSymbol(HIP_SYMBOL(g_gf_prof), &p, sizeof(p)) == hipSuccess ? 0 : -1;
-}
-#endif
-
-extern "C" int zk_gemv_qkv_rope(const void* x, const void* W, int M, int H, int Hkv, int hd, const void* ln_w,
-                                const void* ln_b, float eps, void* q_out, void* k_cache, void* vt_cache, int Smax,
-                                const int32_t* pos_dev, const float* freqs, const int32_t* skip_flag, void* stream) {
-    ZK_REQUIRE(M >= 1 && M <= 2, "zk_gemv_qkv_rope: M=%d (1..2)", M);
-    ZK_REQUIRE(hd == 128 && H % Hkv == 0 && H / Hkv <= AT_G, "zk_gemv_qkv_rope: H=%d Hkv=%d hd=%d", H, Hkv, hd);
-    const int K = H * hd, N = (H + 2 * Hkv) * hd;
-    ZK_REQUIRE(K == 2048, "zk_gemv_qkv_rope: d_model %d (2048 only: the LayerNorm prologue)", K);
-    ZK_REQUIRE(x && W && ln_w && ln_b && q_out && k_cache && vt_cache && pos_dev && freqs,
-               "zk_gemv_qkv_rope: null argument");
-    ZK_REQUIRE(Smax > 0 && Smax % 32 == 0, "zk_gemv_qkv_rope: Smax=%d", Smax);
-    const GfQkv qk{(bf16_t*)k_cache, (bf16_t*)vt_cache, pos_dev, freqs, H, Hkv, Smax};
-    constexpr int KS = 64 / ZK_GF_NW, NL = KS, PB = ZK_GF_PFLN;
-    hipLaunchKernelGGL((k_gemv_f<3, true, 1, false, ZK_GF_NW, KS, (NL < PB ? NL : PB), 0, 2>), dim3(N / 16),
-                       dim3(64 * ZK_GF_NW), 0, (hipStream_t)stream, (const bf16_t*)x, (long)K, (const bf16_t*)W, M, N,
-                       K, (const bf16_t*)ln_w, (const bf16_t*)ln_b, eps, nullptr, (bf16_t*)q_out, skip_flag, nullptr, 1,
-                       qk);
-    ZK_CHECK_LAUNCH("zk_gemv_qkv_rope");
-    return 0;
-}
-
-extern "C" int zk_gemv_attn_out(const float* work, int nsplit, int Hkv, const void* W, int M, int N, int K,
-                                void* x, const int32_t* skip_flag, void* stream) {
-    ZK_REQUIRE(M >= 1 && M <= 2, "zk_gemv_attn_out: M=%d (1..2)", M);
-    ZK_REQUIRE(K == 2048 && N > 0 && N % 16 == 0, "zk_gemv_attn_out: K=%d (2048) N=%d", K, N);
-    ZK_REQUIRE(Hkv >= 1 && (K / 128) % Hkv == 0 && (K / 128) / Hkv <= GF_AT_G, "zk_gemv_attn_out: Hkv=%d", Hkv);
-    ZK_REQUIRE(work != nullptr && x != nullptr, "zk_gemv_attn_out: null buffer");
-    const int grid = 2 * ((N + 15) / 16);                   // half tiles, 8 K-range waves
-#define ZK_GAO(NS_)                                                                                              \
-    hipLaunchKernelGGL((k_gemv_f<2, false, 1, true, 8, 8, 4, NS_, 2>), dim3(grid), dim3(512), 0,               \
-                       (hipStream_t)stream, reinterpret_cast<const bf16_t*>(work), (long)K, (const bf16_t*)W, M,  \
-                       N, K, nullptr, nullptr, 0.f, nullptr, (bf16_t*)x, skip_flag, work, Hkv)
-    switch (nsplit) {
-        case 2: ZK_GAO(2); break;
-        case 4: ZK_GAO(4); break;
-        case 8: ZK_GAO(8); break;
-        case 16: ZK_GAO(16); break;
-        default: ZK_REQUIRE(false, "zk_gemv_attn_out: nsplit=%d (2, 4, 8 or 16)", nsplit);
-    }
-#undef ZK_GAO
-    ZK_CHECK_LAUNCH("zk_gemv_attn_out");
-    return 0;
-}
-
-// L2 warm-up of a k_gemm_ws launch's first weight chunks (experiment): workgroup r of a 1-D grid
-// (same XCD as r % 8) reads, for every GEMM workgroup L = r, r + nwg, ... (same XCD), the first
-// `chunks` 2 KB weight chunks of each of its 4 compute waves, so they are L2 hits when it starts.
+// L2 warm-up of a k_gemm_ws launch's first weight chunks: workgroup r of a 1-D grid (same XCD as r % 8)
+// reads, for every GEMM workgroup L = r, r + nwg, ... (same XCD), the first `chunks` 2 KB weight chunks of
+// each of its compute waves, so they are L2 hits when it starts.
 __global__ __launch_bounds__(256) void k_l2_warm_ws(const bf16_t* __restrict__ W, int K, int gx, int gz, int chunks,
                                                     uint32_t* sink) {
     __shared__ __attribute__((aligned(16))) char lsink[1024];
@@ -1424,19 +1427,14 @@ __global__ __launch_bounds__(256) void k_l2_warm_ws(const bf16_t* __restrict__ W
     (void)sink;
 }
 
+// The GEMM imitated is zk_gemm_bf16(128, N, K, nsplit, 0): its descriptor, as k_resid_ln would be handed it
 extern "C" int zk_l2_warm_gemm(const void* W, int N, int K, int nsplit, int chunks, int nwg, void* sink, void* stream) {
     ZK_REQUIRE(N > 0 && K % (nsplit * BK) == 0 && chunks >= 1 && chunks <= K / nsplit / BK && nwg > 0,
                "zk_l2_warm_gemm: N=%d K=%d nsplit=%d chunks=%d", N, K, nsplit, chunks);
-    hipLaunchKernelGGL(k_l2_warm_ws, dim3(nwg), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)W, K,
-                       (N + BN - 1) / BN, nsplit, chunks, (uint32_t*)sink);
+    const ZkWarm d = zk_gemm_warm_desc(W, BM, N, K, nsplit, 0, chunks);
+    ZK_REQUIRE(d.W != nullptr, "zk_l2_warm_gemm: N=%d K=%d nsplit=%d is outside the decode regime", N, K, nsplit);
+    hipLaunchKernelGGL(k_l2_warm_ws, dim3(nwg), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)W, d.K, d.gx, d.gz,
+                       d.chunks, (uint32_t*)sink);
     ZK_CHECK_LAUNCH("zk_l2_warm_gemm");
-    return 0;
-}
-
-extern "C" int zk_permute_fc1(const void* w_fc1, int F, int D, void* w_out, void* stream) {
-    ZK_REQUIRE(F % 8 == 0 && D % 8 == 0, "zk_permute_fc1: F=%d D=%d", F, D);
-    hipLaunchKernelGGL(k_permute_fc1, dim3(2 * F), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)w_fc1, F, D,
-                       (bf16_t*)w_out);
-    ZK_CHECK_LAUNCH("zk_permute_fc1");
     return 0;
 }

@@ -369,13 +369,6 @@ __global__ __launch_bounds__(PF_NT, 1) void k_gemm_pf(const bf16_t* __restrict__
 
 }  // namespace
 
-// The prefill regime of zk_gemm_bf16 (split 1, large M): true when the 256-row-tile kernel takes the call.
-bool zk_gemm_pf_applies(int M, int N, int K, int nsplit) {
-    if (nsplit != 1 || K % 64 != 0 || N % 64 != 0) return false;
-    const long tiles = (long)((M + PF_BM - 1) / PF_BM) * ((N + 255) / 256);
-    return tiles >= 256;                              // at least one tile per CU
-}
-
 // stage depth and ring length: 64-deep stages x 2. 32-deep x 4 (3 in flight; 128 KB either way)
 // measured 2-4 % slower at the c3 prefill shapes: profiles/r4_prefill_gemm_bks_ab.txt (so the kernel
 // is not waiting on copy latency). 256 x 384 tiles for the SwiGLU (fc1) form measured slower:
@@ -388,6 +381,16 @@ constexpr int pf_lds() {
                   MODE == 1 ? pf_epi_lds1<NTN> : pf_epi_lds0<NTN>);
 }
 static_assert(pf_lds<0, 4>() <= 163840 && pf_lds<1, 4>() <= 163840, "LDS");
+
+// The prefill regime of zk_gemm_bf16 (split 1, large M): true when the 256-row-tile kernel takes the call,
+// with its launch (one workgroup per tile). Called by gemm_plan (gemm.hip) only.
+bool zk_gemm_pf_applies(int M, int N, int K, int nsplit, int mode, long* tiles, int* block, int* lds) {
+    if (nsplit != 1 || K % 64 != 0 || N % 64 != 0) return false;
+    *tiles = (long)((M + PF_BM - 1) / PF_BM) * ((N + 255) / 256);
+    *block = PF_NT;
+    *lds = mode == 0 ? pf_lds<0, 4>() : pf_lds<1, 4>();
+    return *tiles >= 256;                             // at least one tile per CU
+}
 
 template <int MODE, int NTN>
 static int pf_launch(const void* A, long lda, const void* W, int M, int N, int K, float* C, void* Cb,

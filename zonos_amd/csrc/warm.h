@@ -13,10 +13,32 @@ struct ZkWarm {
     const void* W;     // packed weights of the GEMM to warm (nullptr: off)
     int K;             // GEMM K
     int gx, gz;        // its k_gemm_ws grid (column tiles, K splits)
-    int chunks;        // 64-deep chunks per compute wave to warm | column groups per wave (NG) << 8
+    int chunks;        // the packed word below
 };
 
-// k_gemm_ws grid of zk_gemm_bf16(M, N, K, nsplit, mode) in the decode regime, or W = nullptr
+// ZkWarm::chunks is one word, so the warming kernels take five scalars: bits 0-7 64-deep chunks per
+// compute wave to warm, 8-15 column groups per wave (k_gemm_ws NG, 0 = 1), 16-23 compute waves per
+// workgroup of the warmed GEMM (0 = 4), 24-31 trailing 16-column tiles of its grid wholly past N (the
+// packed image holds ceil(N / 16) tiles, padded to 64 columns; a 48-column grid can overshoot even
+// that -- c5 Mamba in_proj: 178 x 3 = 534 tiles for a 532-tile image -- so those are skipped).
+// Packed and unpacked here only, on the host and in the kernels.
+#ifdef __HIPCC__
+#define ZK_WARM_FN __host__ __device__ inline
+#else
+#define ZK_WARM_FN inline
+#endif
+ZK_WARM_FN int warm_pack(int chunks, int ng, int nw, int excess) {
+    return chunks | (ng != 1 ? ng << 8 : 0) | (nw != 4 ? nw << 16 : 0) | (excess << 24);
+}
+ZK_WARM_FN int warm_chunks(int word) { return word & 255; }
+ZK_WARM_FN int warm_ng(int word) { return ((word >> 8) & 255) > 1 ? ((word >> 8) & 255) : 1; }
+ZK_WARM_FN int warm_nw(int word) { return ((word >> 16) & 255) ? ((word >> 16) & 255) : 4; }
+// Compute wave w of the GEMM workgroup in grid column bx streams the 16-column tiles
+// warm_tile(word, bx, w, g), g < NG; the tiles below warm_ntiles hold a column < N.
+ZK_WARM_FN int warm_tile(int word, int bx, int w, int g) { return (bx * warm_nw(word) + w) * warm_ng(word) + g; }
+ZK_WARM_FN int warm_ntiles(int word, int gx) { return gx * warm_nw(word) * warm_ng(word) - ((word >> 24) & 255); }
+
+// k_gemm_ws grid of zk_gemm_bf16(M, N, K, nsplit, mode) when that kernel takes the call with M > 16, or W = nullptr
 ZkWarm zk_gemm_warm_desc(const void* W, int M, int N, int K, int nsplit, int mode, int chunks);
 
 int zk_resid_ln_warm(const float* part, int nsplit, const void* x_in, const void* w, const void* b, float eps,
