@@ -22,7 +22,12 @@ ARCH = os.environ.get("ZK_OFFLOAD_ARCH", "gfx950")
 # -ffp-contract=off: no implicit FMA contraction -- the reference rounds every elementwise op
 # (torch CPU kernels are unfused) and __fmul_rn / __fadd_rn are plain operators in HIP, so
 # contraction would make results depend on how each kernel happens to be scheduled.
-FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wno-unused-result", "-ffp-contract=off"]
+# -amdgpu-kernarg-preload-count: gfx950 delivers a kernel's first argument dwords (up to 14 beside the
+# kernarg pointer) in SGPRs at wave start, so a kernel's front does not begin with an argument load and
+# its wait; firmware without the feature runs the prologue hipcc emits, which loads them as before.
+# Same instructions behind the front, same results ("Kernel-argument preload").
+FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wno-unused-result", "-ffp-contract=off",
+         "-mllvm", "-amdgpu-kernarg-preload-count=16"]
 
 
 def _deps_mtime() -> float:

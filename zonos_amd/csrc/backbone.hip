@@ -292,12 +292,14 @@ __global__ __launch_bounds__(LN_NT) void k_resid_ln_var(const float* part, int n
 // NS > 0: exactly NS slabs (only real slabs loaded); NS = 0: nsplit <= RL_MAXS with clamped loads
 // WARM: a ninth wave warms the next GEMM's first weight chunks into L2 (warm.h) and keeps the
 // block's barrier count (two per row) without waiting for its loads.
+// Argument order: the first 14 dwords arrive preloaded in SGPRs (DESIGN §6 "Kernel-argument preload") and
+// hold everything the row loads and the step-word test need; the outputs and the warm-up descriptor follow.
 template <int NS, bool WARM = false>
-__global__ __launch_bounds__(WARM ? 576 : 512) void k_resid_ln_d2k512(const float* part, int nsplit, const bf16_t* x_in,
-                                                         const bf16_t* w, const bf16_t* b, float eps, int rows,
-                                                         bf16_t* x_out, bf16_t* xn_out, int ln_on_sum,
-                                                         const int32_t* skip, const bf16_t* wW, int wK, int wgx,
-                                                         int wgz, int wch) {
+__global__ __launch_bounds__(WARM ? 576 : 512) void k_resid_ln_d2k512(const float* part, const bf16_t* x_in,
+                                                         const bf16_t* w, const bf16_t* b, const int32_t* skip,
+                                                         int nsplit, int rows, float eps, int ln_on_sum,
+                                                         bf16_t* x_out, bf16_t* xn_out, const bf16_t* wW, int wK,
+                                                         int wgx, int wgz, int wch) {
     constexpr int D = 2048;
     __shared__ float red[16];
     if (WARM && threadIdx.x >= 512)         // (two tests of one condition: folded into one block, hipcc
@@ -603,9 +605,9 @@ int zk_resid_ln_warm(const float* part, int nsplit, const void* x_in, const void
         auto kern = wm ? (nsplit == 4 ? k_resid_ln_d2k512<4, true> : nsplit == 8 ? k_resid_ln_d2k512<8, true>
                                                                                 : k_resid_ln_d2k512<0, true>)
                        : (nsplit == 4 ? k_resid_ln_d2k512<4> : nsplit == 8 ? k_resid_ln_d2k512<8> : k_resid_ln_d2k512<0>);
-        hipLaunchKernelGGL(kern, dim3(rows), dim3(wm ? 576 : 512), 0, (hipStream_t)stream, part, nsplit,
-                           (const bf16_t*)x_in, (const bf16_t*)w, (const bf16_t*)b, eps, rows, (bf16_t*)x_out,
-                           (bf16_t*)xn_out, ln_on_sum, skip, (const bf16_t*)warm.W, warm.K, warm.gx, warm.gz,
+        hipLaunchKernelGGL(kern, dim3(rows), dim3(wm ? 576 : 512), 0, (hipStream_t)stream, part,
+                           (const bf16_t*)x_in, (const bf16_t*)w, (const bf16_t*)b, skip, nsplit, rows, eps, ln_on_sum,
+                           (bf16_t*)x_out, (bf16_t*)xn_out, (const bf16_t*)warm.W, warm.K, warm.gx, warm.gz,
                            warm.chunks);
         ZK_CHECK_LAUNCH("zk_resid_ln");
         return 0;

@@ -14,8 +14,10 @@ typedef uint16_t f16_t;
 // A nullable device int32 (skip / context / offset words) read without a branch and as a VECTOR
 // load (relaxed atomic: never scalarised), issued before the kernel's data loads: vmcnt retires in
 // issue order, so the test of the word waits for it alone, where a scalar load's wait (lgkmcnt(0),
-// scalar loads return out of order) would also hold every later kernel-argument load. Each lane
-// holds the same value; callers take it with readfirstlane where they branch or index on it.
+// scalar loads return out of order) would also hold every later kernel-argument load -- of an
+// argument behind the first 14 dwords, that is: those arrive in SGPRs at wave start (kernel-argument
+// preload, build.py FLAGS) and are never loaded. Each lane holds the same value; callers take it
+// with readfirstlane where they branch or index on it.
 static __device__ int32_t zk_zero_word = 0;    // never written; not const, so the load is not folded
 ZK_DEV int32_t ld_word(const int32_t* p) {
     return __hip_atomic_load(p != nullptr ? p : &zk_zero_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

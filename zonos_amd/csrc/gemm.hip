@@ -280,20 +280,24 @@ constexpr int ws_nld(int ncw, int mt) {
 template <int NCW, int MT>
 constexpr int ws_nld() { return ws_nld(NCW, MT); }
 template <int MODE, int NCH, int PF, int MT, int NCW = 4, int NG = 1, int NB = (NCW > 5 ? 1 : 2)>
-__global__ __launch_bounds__(64 * (NCW + ws_nld<NCW, MT>()), WS_OCC) void k_gemm_ws(const bf16_t* __restrict__ A, long lda,
-                                                           const bf16_t* __restrict__ W, int M, int N, int K,
-                                                           int kslice, float* __restrict__ Cpart,
-                                                           bf16_t* __restrict__ Cout, const int32_t* skip,
+__global__ __launch_bounds__(64 * (NCW + ws_nld<NCW, MT>()), WS_OCC) void k_gemm_ws(const bf16_t* __restrict__ A, const int32_t* skip,
+                                                           const bf16_t* __restrict__ W, long lda, int M, int N, int K,
+                                                           int kslice, int gx, int gz, float* __restrict__ Cpart,
+                                                           bf16_t* __restrict__ Cout,
                                                            const bf16_t* __restrict__ wW, int wK, int wgx, int wgz,
                                                            int wch) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
+    // (argument order: the first 14 dwords arrive preloaded in SGPRs, DESIGN §6 "Kernel-argument preload" --
+    // the skip pointer and everything that addresses the first loads are among them, the grid gx x 1 x gz
+    // too, which as gridDim would be a load from the hidden arguments behind the skip test; the output
+    // pointers and the warm-up descriptor, used behind the K loop, are not)
     // (the skip word is tested first here: deferring the test behind the first loads, as k_gemv_f
     // does, measured 0.3-1.2 % slower per c3 step with a vector or a scalar load of the word,
     // profiles/r3s2_skip_defer_ab.txt; again in round 6, 3.500-3.510 vs 3.473-3.489 ms, while k_resid_ln gained:
     // profiles/r6_c3_gemm_ws_defer_ab.txt)
     if (skip && *skip) return;
     int bx, bz;
-    ws_tile(blockIdx.x + gridDim.x * blockIdx.z, gridDim.x, gridDim.z, bx, bz);     // gridDim.y == 1
+    ws_tile(blockIdx.x + gx * blockIdx.z, gx, gz, bx, bz);
     constexpr int BNW = 16 * NCW * NG;            // columns per workgroup
     const int n0 = bx * BNW, split = bz;
     const int kbeg = split * kslice;
@@ -347,7 +351,7 @@ __global__ __launch_bounds__(64 * (NCW + ws_nld<NCW, MT>()), WS_OCC) void k_gemm
             // the loaders, idle from here on, stream their compute waves' first chunks into L2 (LDS-DMA
             // into the 1 KB sink past the ring), then keep the workgroup's barrier count: the epilogue's
             // two __syncthreads must not wait for these loads
-            warm_units(wW, wK, wgx, wgz, wch, blockIdx.x + gridDim.x * blockIdx.z, gridDim.x * gridDim.z, ld, NLD,
+            warm_units(wW, wK, wgx, wgz, wch, blockIdx.x + gx * blockIdx.z, gx * gz, ld, NLD,
                        lane, smem + WS_NB * (MT * 16 * BK * 2));
             if (MODE == 1 || N % 4 == 0) {
                 __builtin_amdgcn_s_barrier();
@@ -1190,14 +1194,21 @@ int gemm_launch(const GemmPlan& p, const void* A, long lda, const void* W, int M
                 float* Cpart, void* Cout, const int32_t* skip_flag, ZkWarm warm, hipStream_t stream) {
     if (p.family == GEMM_PF) return zk_gemm_pf(A, lda, W, M, N, K, p.mode, Cpart, Cout, skip_flag, stream);
     bool launched = false;
-    auto launch = [&](auto kern, size_t lds, auto... more) {
-        hipLaunchKernelGGL(kern, dim3((unsigned)p.gx, p.gy, p.gz), dim3(p.block), lds, stream, (const bf16_t*)A, lda,
-                           (const bf16_t*)W, M, N, K, K / nsplit, Cpart, (bf16_t*)Cout, skip_flag, more...);
+    auto launch = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3((unsigned)p.gx, p.gy, p.gz), dim3(p.block), 0, stream, (const bf16_t*)A, lda,
+                           (const bf16_t*)W, M, N, K, K / nsplit, Cpart, (bf16_t*)Cout, skip_flag);
+        launched = true;
+    };
+    // k_gemm_ws takes its arguments in its own order (what its front needs first, the grid included)
+    auto launch_ws = [&](auto kern, size_t lds) {
+        hipLaunchKernelGGL(kern, dim3((unsigned)p.gx, 1, p.gz), dim3(p.block), lds, stream, (const bf16_t*)A, skip_flag,
+                           (const bf16_t*)W, lda, M, N, K, K / nsplit, (int)p.gx, p.gz, Cpart, (bf16_t*)Cout,
+                           (const bf16_t*)warm.W, warm.K, warm.gx, warm.gz, warm.chunks);
         launched = true;
     };
     if (p.family == GEMM_RK)
         pick([&](auto mode, auto ks) {
-            if constexpr (rk_has(mode(), ks())) launch(&k_gemv_rk<mode(), 2, ks(), rk_pf(ks())>, 0);
+            if constexpr (rk_has(mode(), ks())) launch(&k_gemv_rk<mode(), 2, ks(), rk_pf(ks())>);
         }, p.mode, Ints<0, 1>{}, p.ks, Ints<1, 2, 4, 8, 16>{});
     else if (p.family == GEMM_WS)
         pick([&](auto mode, auto nch, auto mt, auto ncw) {
@@ -1207,13 +1218,13 @@ int gemm_launch(const GemmPlan& p, const void* A, long lda, const void* W, int M
                 if (lds > 65536)
                     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                launch(kern, lds, (const bf16_t*)warm.W, warm.K, warm.gx, warm.gz, warm.chunks);
+                launch_ws(kern, lds);
             }
         }, p.mode, Ints<0, 1>{}, p.nchunks, Ints<2, 4, 8, 16, 32>{}, p.mt, Ints<1, 2, 4, 8>{}, p.ncw,
              Ints<2, 3, (ZK_WS_WIDE > 0 ? ZK_WS_WIDE : ZK_WS_NCW), ZK_WS_NCW>{});
     else
         pick([&](auto mode, auto u, auto ntw) {
-            if constexpr (tile_has(mode(), u(), ntw())) launch(&k_gemm<mode(), u(), ntw()>, 0);
+            if constexpr (tile_has(mode(), u(), ntw())) launch(&k_gemm<mode(), u(), ntw()>);
         }, p.mode, Ints<0, 1>{}, p.u, Ints<1, 2, 4>{}, p.ntw, Ints<1, 2>{});
     ZK_REQUIRE(launched, "zk_gemm_bf16: no kernel for the plan (family %d)", (int)p.family);
     ZK_CHECK_LAUNCH("zk_gemm_bf16");
