@@ -510,7 +510,8 @@ int zk_dac_rvq_decode_cl(const int64_t* codes, int B, int ncb, int T, long code_
  * W_r = w + r*w_phase_stride (zk_dac_prep_w16 hi layout). Inputs outside [0, lens[b]*in_scale)
  * read 0; outputs at t >= lens[b]*out_scale are written 0. Cin, Cout % 32 == 0; ks <= 7,
  * (ks-1)*dil <= 64. Conv1d: nphase=1, out_stride=1, out_off0=0. ConvTranspose1d(stride s):
- * ks=2, dil=1, pad=1, Qn=Tin+1, nphase=s, out_stride=s, out_off0=-ceil(s/2). */
+ * ks=2, dil=1, pad=1, Qn=Tin+1, nphase=s, out_stride=s, out_off0=-ceil(s/2).
+ * How a shape is launched (workgroup shape, tile, LDS, tiles): zk_dac_conv_plan below. */
 int zk_dac_conv_cl(const uint16_t* in, int B, int Cin, int Tin, const uint16_t* w, long w_phase_stride,
                    const float* bias, int Cout, int ks, int dil, int pad, int Qn, int nphase,
                    int out_stride, int out_off0, int Tout, const float* resid, float* x_out,
@@ -531,6 +532,18 @@ int zk_dac_resunit_supported(int C);
 int zk_dac_resunit_cl(const uint16_t* s_in, int B, int C, int T, const uint16_t* w7, const float* b7, int dil,
                       const float* a2, const uint16_t* w1, const float* b1, float* x, const float* alpha_next,
                       void* s_out, int s_f32, const int32_t* lens, int scale, void* stream);
+/* The launch plan of zk_dac_conv_cl (fused = 0; resid, s_f32: whether it gets a residual / writes the fp32
+ * Snake) or of zk_dac_resunit_cl (fused = 1: C = Cout, T = Qn; Cin, ks, nphase, resid are not read), by the
+ * entries' own shape checks and rule. Host only: no GPU is touched. Fills plan[ZK_DAC_PLAN_N]:
+ *   0 workgroup shape (0 pair: two per CU, 1 fat: one per CU, 2 fused C = 96, 3 fused C = 192)
+ *   1 FM (16-row MFMA blocks of output channels per wave)   2 positions per tile
+ *   3 dx (steps the input windows are loaded ahead)         4 nx (window ring slots)
+ *   5 dynamic LDS bytes per workgroup                       6 position tiles per row
+ *   7 tiles in all = B * [6] * channel tiles * nphase       8 workgroups per CU the shape is built for
+ * Returns 0, or -1 with zk_last_error set where the entry would refuse the shape. */
+#define ZK_DAC_PLAN_N 9
+int zk_dac_conv_plan(int fused, int B, int Cin, int Cout, int ks, int dil, int Qn, int nphase, int resid,
+                     int s_f32, int32_t* plan);
 /* out[b][t] = tanh(bias + sum_{c,k} w[c*7+k] * s[b][t+k-3][c]), 0 at t >= lens[b]*scale
  * (s = fp32 output of the final Snake, zk_dac_conv_cl with s_f32 = 1; modeling_dac.py:437-439). */
 int zk_dac_tail_cl(const float* s, int B, int C, int T, const float* w, const float* bias,

@@ -147,17 +147,14 @@ def _long():
     return dec, d, codes, wav, wav_s
 
 
-def _tiles_per_workgroup(B, Qn, Cout, resid=False, nphase=1):
-    """Tiles each persistent workgroup of zk_dac_conv_cl streams at least (dac_cl.hip launch_conv:
-    grid = min(tiles, resident workgroups); the fat 12-wave form holds one workgroup per CU on
-    512-position tiles, the others at most two per CU on 128-position tiles)."""
-    nco = Cout // 32
-    FM = 4 if nco % 4 == 0 else 3 if nco % 3 == 0 else 2 if nco % 2 == 0 else 1
-    fat = not resid and nphase == 1 and FM <= 3
-    qt = 512 if fat else 128
-    ntiles = B * (-(-Qn // qt)) * (Cout // (32 * FM)) * nphase
+def _tiles_per_workgroup(B, Qn, C, resid=False, fused=False):
+    """Tiles each persistent workgroup streams at least, for a C-channel stage's k7 conv, its 1x1 + residual
+    conv (resid) or its fused residual unit (fused), by the library's own launch plan (zk_dac_conv_plan:
+    grid = min(tiles, resident workgroups), resident = the workgroups per CU the shape is built for)."""
+    from zonos_amd import _lib
+    p = _lib.dac_conv_plan(B, C, C, 1 if resid else 7, 1, Qn, resid=resid, fused=fused)
     ncu = torch.cuda.get_device_properties(0).multi_processor_count
-    return ntiles // (ncu * (1 if fat else 2))
+    return p["tiles"] // (ncu * p["wg_per_cu"])
 
 
 def test_dac_long_golden_multitile():
@@ -217,9 +214,8 @@ def test_dac_long_fused_units_equal_unfused_to_rounding(monkeypatch):
     from zonos_amd import _lib
     dec, d, codes, wav, _ = _long()
     assert _lib.load().zk_dac_resunit_supported(96) >= 1
-    # the fused unit's grid: 512-position tiles, one workgroup per CU -> >= 2 tiles each at this length
-    ncu = torch.cuda.get_device_properties(0).multi_processor_count
-    assert 2 * (-(-512 * codes.shape[2] // 512)) >= 2 * ncu
+    # the fused unit's grid (512-position tiles, one workgroup per CU): >= 2 tiles each at this length
+    assert _tiles_per_workgroup(2, 512 * codes.shape[2], 96, fused=True) >= 2
     monkeypatch.setattr(HipDacDecoder, "c_dac", False)
     outs = []
     for fuse in (True, False):

@@ -58,21 +58,17 @@ MULTITILE_CASES = [
 ]
 
 
-def _min_tiles_per_wg(B, T, Cout, resid):
-    nco = Cout // 32
-    FM = 4 if nco % 4 == 0 else 3 if nco % 3 == 0 else 2 if nco % 2 == 0 else 1
-    fat = not resid and FM <= 3
-    qt = 512 if fat else 128
-    ntiles = B * (-(-T // qt)) * (Cout // (32 * FM))
+def _min_tiles_per_wg(plan):
+    """Tiles per persistent workgroup, from the library's own launch plan (zk_dac_conv_plan)."""
     ncu = torch.cuda.get_device_properties(0).multi_processor_count
-    return ntiles // (ncu * (1 if fat else 2))
+    return plan["tiles"] // (ncu * plan["wg_per_cu"])
 
 
 @pytest.mark.parametrize("Cin,Cout,ks,dil,T,use_resid", CONV_CASES + MULTITILE_CASES)
 def test_conv_cl_vs_torch(Cin, Cout, ks, dil, T, use_resid):
     L = _lib()
     if T >= 4000:
-        assert _min_tiles_per_wg(3, T, Cout, use_resid) >= 2
+        assert _min_tiles_per_wg(L.dac_conv_plan(3, Cin, Cout, ks, dil, T, resid=use_resid)) >= 2
     torch.manual_seed(Cin + Cout + ks + dil)
     dev = "cuda"
     B = 3
@@ -120,9 +116,8 @@ def test_resunit_fused_vs_pair_and_torch(C, dil, T):
     L = _lib()
     B, dev = 3, "cuda"
     assert L.load().zk_dac_resunit_supported(384) == 0      # (96 / 192: the product fuses, variants may not)
-    ncu = torch.cuda.get_device_properties(0).multi_processor_count
     if T >= 50000:
-        assert B * (-(-T // (512 if C == 96 else 256))) >= 2 * ncu
+        assert _min_tiles_per_wg(L.dac_conv_plan(B, C, C, 7, dil, T, fused=True)) >= 2
     torch.manual_seed(C + dil * 1000 + T)
     st = L.stream_ptr(torch.device(dev))
     lens = torch.tensor([T, T // 2, 1], dtype=torch.int32, device=dev)

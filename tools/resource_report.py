@@ -1,7 +1,10 @@
 """Print per-kernel VGPR / scratch / occupancy of the HIP sources (hipcc -Rpass-analysis), or with
---preload each kernel's kernel-argument preload and what its front still loads.
+--preload each kernel's kernel-argument preload and what its front still loads, or with --asm-diff REV
+whether each source's device assembly equals that of the same file at git revision REV (a refactor's check).
 
-Developer tool, not part of the product package: `python tools/resource_report.py [--preload] [SRC ...]`."""
+Developer tool, not part of the product package:
+`python tools/resource_report.py [--preload | --asm-diff REV] [SRC ...]`."""
+import difflib
 import os
 import re
 import shutil
@@ -32,11 +35,11 @@ def report(src: str) -> None:
                     print(f"{src:12s} {cur[:60]:60s} {info}{flag}")
 
 
-def device_asm(src: str) -> str:
+def device_asm(src: str, csrc: str = CSRC) -> str:
     """The device-only assembly of one source, built with the library's own flags."""
     with tempfile.TemporaryDirectory() as d:
         out = os.path.join(d, "k.s")
-        r = subprocess.run([HIPCC, *FLAGS, "--cuda-device-only", "-S", os.path.join(CSRC, src), "-o", out],
+        r = subprocess.run([HIPCC, *FLAGS, "--cuda-device-only", "-S", os.path.join(csrc, src), "-o", out],
                            capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError(f"hipcc -S failed for {src}:\n{r.stderr}")
@@ -103,7 +106,53 @@ def report_preload(src: str) -> None:
         print(f"{src:12s} {nice[name][:72]:72s} preload {k['preload']:2d} dw of {k['kernarg'] // 4:3d}  front loads {front}")
 
 
+def kernel_texts(asm: str) -> dict:
+    """Per kernel (mangled name): its code and kernel descriptor with the names a renaming changes taken out --
+    the kernel's own symbol, the function numbers in local labels, the per-build __hip_cuid_* symbol."""
+    out = {}
+    for m in re.finditer(r"^(\w+):[^\n]*\n.*?^\s*\.amdhsa_kernel \1\n.*?^\s*\.end_amdhsa_kernel", asm, re.M | re.S):
+        text = m.group(0).replace(m.group(1), "KERNEL")
+        text = re.sub(r"\.L([A-Za-z_]+)\d+", r".L\1", re.sub(r"\bBB\d+_", "BB_", text))
+        out[m.group(1)] = re.sub(r"[ \t]+", " ", re.sub(r"__hip_cuid_\w+", "__hip_cuid", text))   # (comment padding)
+    return out
+
+
+def asm_diff(src: str, rev: str) -> bool:
+    """Compare src's kernels with those of the same file at `rev` (its whole csrc/ and include/ of that
+    revision), as multisets of normalised texts: names may change, code may not."""
+    root = os.path.dirname(os.path.dirname(CSRC))
+    with tempfile.TemporaryDirectory() as d:
+        tar = subprocess.run(["git", "-C", root, "archive", rev, "zonos_amd/csrc", "include"], capture_output=True, check=True)
+        subprocess.run(["tar", "-x", "-C", d], input=tar.stdout, check=True)
+        old = kernel_texts(device_asm(src, os.path.join(d, "zonos_amd", "csrc")))
+    new = kernel_texts(device_asm(src))
+    nice = demangle(list(new) + list(old))
+    left = dict(old)
+    for name, text in new.items():
+        twin = next((o for o, t in left.items() if t == text), None)
+        if twin is not None:
+            del left[twin]
+            continue
+        print(f"{src}: DIFFERS at {nice[name][:100]}")
+        if left:
+            near = max(left, key=lambda o: difflib.SequenceMatcher(None, left[o], text, autojunk=False).quick_ratio())
+            delta = list(difflib.unified_diff(left[near].split("\n"), text.split("\n"), nice[near][:60], "new", n=0, lineterm=""))
+            print(f"  nearest of {rev}: {nice[near][:100]} ({len(delta)} diff lines)")
+            print("\n".join("  " + ln for ln in delta[:20]))
+        return False
+    if left:
+        print(f"{src}: DIFFERS: {len(left)} kernels of {rev} are gone, first {nice[next(iter(left))][:100]}")
+        return False
+    print(f"{src}: identical ({len(new)} kernels)")
+    return True
+
+
 def main(argv) -> None:
+    if "--asm-diff" in argv:
+        i = argv.index("--asm-diff")
+        rev, srcs = argv[i + 1], argv[:i] + argv[i + 2:]
+        srcs = srcs or sorted(s for s in os.listdir(CSRC) if s.endswith(".hip"))
+        sys.exit(0 if all([asm_diff(src, rev) for src in srcs]) else 1)
     preload = "--preload" in argv
     argv = [a for a in argv if a != "--preload"]
     srcs = argv or sorted(s for s in os.listdir(CSRC) if s.endswith(".hip"))

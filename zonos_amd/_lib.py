@@ -156,6 +156,7 @@ _SIGS = {
     "zk_dac_tail": [P, I, I, I, P, P, P, P, P, I, P],
     "zk_dac_rvq_decode_cl": [P, I, I, I, L, P, I, I, I, P, P, P],
     "zk_dac_conv_cl": [P, I, I, I, P, L, P, I, I, I, I, I, I, I, I, I, P, P, P, P, I, P, I, I, P],
+    "zk_dac_conv_plan": [I, I, I, I, I, I, I, I, I, I, P],
     "zk_dac_tail_cl": [P, I, I, I, P, P, P, P, I, P],
     "zk_dac_resunit_cl": [P, I, I, I, P, P, I, P, P, P, P, P, P, I, P, I, P],
     "zk_dac_enc_conv1": [P, I, I, P, P, P, I, I, P, P, P],
@@ -228,6 +229,16 @@ def call(name: str, *args):
     if rc != 0:
         raise ZonosHipError(f"{name} failed ({rc}): {lib.zk_last_error().decode()}")
     return rc
+
+
+DAC_PLAN_FIELDS = ("shape", "fm", "tile", "dx", "nx", "lds", "nq", "tiles", "wg_per_cu")   # ZK_DAC_PLAN_N = 9
+
+
+def dac_conv_plan(B, Cin, Cout, ks, dil, Qn, nphase=1, resid=False, s_f32=False, fused=False) -> dict:
+    """zk_dac_conv_plan: how zk_dac_conv_cl (fused: zk_dac_resunit_cl, C = Cout, T = Qn) launches a shape. No GPU."""
+    plan = (C.c_int32 * len(DAC_PLAN_FIELDS))()
+    call("zk_dac_conv_plan", int(fused), B, Cin, Cout, ks, dil, Qn, nphase, int(resid), int(s_f32), plan)
+    return dict(zip(DAC_PLAN_FIELDS, plan))
 
 
 def ptr(t) -> int | None:

@@ -61,6 +61,53 @@ def _fold_weight_norm(sd: dict) -> dict:
     return out
 
 
+# ---- the channels-last convs (dac_cl.hip), shared by decoder and encoder
+def _pad32(c):
+    return (c + 31) // 32 * 32
+
+
+def _vec32(v, fill):
+    """A per-channel vector padded to a multiple of 32 channels (biases with 0, Snake alphas with 1)."""
+    out = torch.full((_pad32(v.numel()),), fill, device=v.device)
+    out[:v.numel()] = v.reshape(-1)
+    return out
+
+
+def _wconv16(w, nphase=1, mode=0):
+    """fp32 conv weights, channels zero-padded to multiples of 32: [Cout][Cin][ks] -> fp16 [ks][Cout_p][Cin_p];
+    mode 1 (ConvTranspose1d): [Cin][Cout][2 nphase] -> fp16 [nphase][2][Cout_p][Cin_p]."""
+    wp = torch.zeros(_pad32(w.shape[0]), _pad32(w.shape[1]), w.shape[2], device=w.device)
+    wp[:w.shape[0], :w.shape[1]] = w
+    co, ci, ks = (wp.shape[1], wp.shape[0], 2) if mode else wp.shape
+    out = torch.empty(nphase * ks * co * ci, dtype=torch.int16, device=w.device)
+    call("zk_dac_prep_w16", ptr(wp), co, ci, ks, nphase, mode, ptr(out), None, _lib.stream_ptr(w.device))
+    return out
+
+
+# The three uses of zk_dac_conv_cl. s: fp16 Snake'd activations [B][L][Cin]; every conv applies the next Snake
+# (alpha) in its epilogue; lens counts frames (None: all), `scale` samples per frame at this stage.
+def _conv_k7(s, w, b, dil, alpha, s_out, lens, scale, stream):
+    """k7 conv, dilated, 'same' padding: s_out = fp16 Snake(conv(s) + b)."""
+    B, L, cin = s.shape
+    call("zk_dac_conv_cl", ptr(s), B, cin, L, ptr(w), 0, ptr(b), s_out.shape[2], 7, dil, 3 * dil, L, 1, 1, 0, L,
+         None, None, ptr(alpha), ptr(s_out), 0, ptr(lens), scale, scale, stream)
+
+
+def _conv_1x1_res(s, w, b, x, alpha, s_out, lens, scale, stream):
+    """1x1 conv + residual: x += conv(s) + b, s_out = Snake(x), fp16 or (an fp32 s_out: the tail's input) fp32."""
+    B, L, c = s.shape
+    call("zk_dac_conv_cl", ptr(s), B, c, L, ptr(w), 0, ptr(b), c, 1, 1, 0, L, 1, 1, 0, L, ptr(x), ptr(x), ptr(alpha),
+         ptr(s_out), int(s_out.dtype == torch.float32), ptr(lens), scale, scale, stream)
+
+
+def _convt(s, w, b, st, x, alpha, s_out, lens, scale, stream):
+    """ConvTranspose1d(k = 2 st, stride st) as st 2-tap convs, L -> L st: x = conv(s) + b, s_out = fp16 Snake(x)."""
+    B, L, cin = s.shape
+    cout = x.shape[2]
+    call("zk_dac_conv_cl", ptr(s), B, cin, L, ptr(w), 2 * cout * cin, ptr(b), cout, 2, 1, 1, L + 1, st, st,
+         -((st + 1) // 2), L * st, None, ptr(x), ptr(alpha), ptr(s_out), 0, ptr(lens), scale, scale * st, stream)
+
+
 class HipDacDecoder:
     """Decoder weights on the device + the launch sequence of the DAC decoder.
 
@@ -112,7 +159,7 @@ class HipDacDecoder:
         self.final_alpha = t("decoder.snake1.alpha").reshape(-1)
         self.conv2_w, self.conv2_b = t("decoder.conv2.weight"), t("decoder.conv2.bias")
         if precision == "fp16":
-            self._prep_cl(stream)
+            self._prep_cl()
         elif precision != "fp32":
             self.w16 = {}
             self._prep16("conv1", self.conv1_w, 0, stream)
@@ -124,45 +171,19 @@ class HipDacDecoder:
         torch.cuda.synchronize(dev)
 
     # ---------------------------------------------------------------- channels-last fp16 path
-    @staticmethod
-    def _pad32(c):
-        return (c + 31) // 32 * 32
-
-    def _prep_cl(self, stream):
+    def _prep_cl(self):
         """Weights for dac_cl.hip: channels zero-padded to multiples of 32, fp16 [tap][Cout][Cin]
         (ConvTranspose1d: [phase][2][Cout][Cin]); biases padded with 0, Snake alphas with 1."""
-        dev, s, P = self.device, self.spec, self._pad32
-
-        def wconv(w):                       # [Cout][Cin][ks] -> fp16 [ks][Cout_p][Cin_p]
-            co, ci, ks = w.shape
-            wp = torch.zeros(P(co), P(ci), ks, device=dev)
-            wp[:co, :ci] = w
-            out = torch.empty(ks * P(co) * P(ci), dtype=torch.int16, device=dev)
-            call("zk_dac_prep_w16", ptr(wp), P(co), P(ci), ks, 1, 0, ptr(out), None, stream)
-            return out
-
-        def wconvt(w, st):                  # [Cin][Cout][2s] -> fp16 [s][2][Cout_p][Cin_p]
-            ci, co, _ = w.shape
-            wp = torch.zeros(P(ci), P(co), 2 * st, device=dev)
-            wp[:ci, :co] = w
-            out = torch.empty(st * 2 * P(co) * P(ci), dtype=torch.int16, device=dev)
-            call("zk_dac_prep_w16", ptr(wp), P(co), P(ci), 2, st, 1, ptr(out), None, stream)
-            return out
-
-        def vec(v, fill):
-            out = torch.full((P(v.numel()),), fill, device=dev)
-            out[:v.numel()] = v.reshape(-1)
-            return out
-
-        cl = {"cin0": P(s.hidden_size), "c0": P(self.conv1_w.shape[0]), "conv1_w": wconv(self.conv1_w),
+        dev, s, P, vec = self.device, self.spec, _pad32, _vec32
+        cl = {"cin0": P(s.hidden_size), "c0": P(self.conv1_w.shape[0]), "conv1_w": _wconv16(self.conv1_w),
               "conv1_b": vec(self.conv1_b, 0.0), "blocks": []}
         for blk in self.blocks:
             st = blk["stride"]
             b = {"stride": st, "cin": P(blk["cin"]), "cout": P(blk["cout"]), "alpha": vec(blk["alpha"], 1.0),
-                 "wt": wconvt(self._convt_raw[len(cl["blocks"])], st), "bt": vec(blk["bt"], 0.0), "res": []}
+                 "wt": _wconv16(self._convt_raw[len(cl["blocks"])], st, 1), "bt": vec(blk["bt"], 0.0), "res": []}
             for ru in blk["res"]:
-                b["res"].append({"dil": ru["dil"], "a1": vec(ru["a1"], 1.0), "w1": wconv(ru["w1"]),
-                                 "b1": vec(ru["b1"], 0.0), "a2": vec(ru["a2"], 1.0), "w2": wconv(ru["w2"]),
+                b["res"].append({"dil": ru["dil"], "a1": vec(ru["a1"], 1.0), "w1": _wconv16(ru["w1"]),
+                                 "b1": vec(ru["b1"], 0.0), "a2": vec(ru["a2"], 1.0), "w2": _wconv16(ru["w2"]),
                                  "b2": vec(ru["b2"], 0.0)})
             cl["blocks"].append(b)
         cl["final_alpha"] = vec(self.final_alpha, 1.0)
@@ -223,19 +244,15 @@ class HipDacDecoder:
         blocks = cl["blocks"]
         a_next = blocks[0]["alpha"] if blocks else cl["final_alpha"]
         act = torch.empty(B, T, cl["c0"], dtype=f16, device=dev)
-        call("zk_dac_conv_cl", ptr(z), B, cl["cin0"], T, ptr(cl["conv1_w"]), 0, ptr(cl["conv1_b"]), cl["c0"], 7, 1, 3,
-             T, 1, 1, 0, T, None, None, ptr(a_next), ptr(act), 0, ptr(lens), 1, 1, stream)
+        _conv_k7(z, cl["conv1_w"], cl["conv1_b"], 1, a_next, act, lens, 1, stream)
         del z
         L, scale = T, 1
         for bi, blk in enumerate(blocks):
-            st, cin, cout = blk["stride"], blk["cin"], blk["cout"]
+            st, cout = blk["stride"], blk["cout"]
             Lo = L * st
             x = torch.empty(B, Lo, cout, device=dev)
             s_new = torch.empty(B, Lo, cout, dtype=f16, device=dev)
-            a1 = blk["res"][0]["a1"]
-            call("zk_dac_conv_cl", ptr(act), B, cin, L, ptr(blk["wt"]), 2 * cout * cin, ptr(blk["bt"]), cout, 2, 1, 1,
-                 L + 1, st, st, -((st + 1) // 2), Lo, None, ptr(x), ptr(a1), ptr(s_new), 0, ptr(lens), scale,
-                 scale * st, stream)
+            _convt(act, blk["wt"], blk["bt"], st, x, blk["res"][0]["a1"], s_new, lens, scale, stream)
             act = s_new
             scale *= st
             L = Lo
@@ -259,12 +276,10 @@ class HipDacDecoder:
                          stream)
                     act, tmp = out, act
                     continue
-                call("zk_dac_conv_cl", ptr(act), B, cout, L, ptr(ru["w1"]), 0, ptr(ru["b1"]), cout, 7, d, 3 * d, L,
-                     1, 1, 0, L, None, None, ptr(ru["a2"]), ptr(tmp), 0, ptr(lens), scale, scale, stream)
+                _conv_k7(act, ru["w1"], ru["b1"], d, ru["a2"], tmp, lens, scale, stream)
                 if last:       # the tail's input: fp32 Snake output (keeps the waveform at fp32-level error)
                     act = torch.empty(B, L, cout, device=dev)
-                call("zk_dac_conv_cl", ptr(tmp), B, cout, L, ptr(ru["w2"]), 0, ptr(ru["b2"]), cout, 1, 1, 0, L,
-                     1, 1, 0, L, ptr(x), ptr(x), ptr(a_next), ptr(act), int(last), ptr(lens), scale, scale, stream)
+                _conv_1x1_res(tmp, ru["w2"], ru["b2"], x, a_next, act, lens, scale, stream)
             del tmp, x
         out = torch.empty(B, 1, L, device=dev)
         call("zk_dac_tail_cl", ptr(act), B, act.shape[2], L, ptr(cl["conv2_w"]), ptr(cl["conv2_b"]), ptr(out),
@@ -368,7 +383,7 @@ class HipDacDecoder:
             Tmax = items[order[i]].shape[1]
             # live activations at the widest-time stage: channels-last fp32 x + 2 fp16 (+ the
             # previous stage's fp16 input) ~ 10 B per (position, channel); channels-first fp32 ~ 12 B
-            per_bytes = (10 if self.precision == "fp16" else 12) * self._pad32(width) * hop * Tmax
+            per_bytes = (10 if self.precision == "fp16" else 12) * _pad32(width) * hop * Tmax
             per = max(1, int(max_batch_bytes // per_bytes))
             grp = order[i:i + per]
             codes = torch.zeros(len(grp), self.spec.n_codebooks, Tmax, dtype=torch.int64, device=self.device)
@@ -398,23 +413,10 @@ class HipDacEncoder:
         self.spec = spec
         self.device = dev = torch.device(device)
         sd = _fold_weight_norm(state_dict)
-        P = HipDacDecoder._pad32
-        stream = _lib.stream_ptr(dev)
+        P, vec = _pad32, _vec32
 
         def t(k):
             return sd[k].to(device=dev, dtype=torch.float32).contiguous()
-
-        def w16(w):                          # fp32 [Cout][Cin][ks] (padded) -> fp16 [ks][Cout][Cin]
-            co, ci, ks = w.shape
-            out = torch.empty(ks * co * ci, dtype=torch.int16, device=dev)
-            call("zk_dac_prep_w16", ptr(w.contiguous()), co, ci, ks, 1, 0, ptr(out), None, stream)
-            return out
-
-        def wconv(w):
-            co, ci, ks = w.shape
-            wp = torch.zeros(P(co), P(ci), ks, device=dev)
-            wp[:co, :ci] = w
-            return w16(wp)
 
         def wstrided(w, st):                 # [Cout][Cin][2s] -> folded 3-tap [Cout_p][s*Cin_p][3]
             co, ci, k2 = w.shape
@@ -426,12 +428,7 @@ class HipDacEncoder:
                     k = (tap - 1) * st + j + st // 2
                     if 0 <= k < k2:
                         wf[:co, j, :ci, tap] = w[:, :, k]
-            return w16(wf.reshape(P(co), st * cip, 3))
-
-        def vec(v, fill):
-            out = torch.full((P(v.numel()),), fill, device=dev)
-            out[:v.numel()] = v.reshape(-1)
-            return out
+            return _wconv16(wf.reshape(P(co), st * cip, 3))
 
         w1 = t("encoder.conv1.weight")
         self.c0 = w1.shape[0]
@@ -446,15 +443,16 @@ class HipDacEncoder:
                    "w": wstrided(wb, st), "b": vec(t(p + "conv1.bias"), 0.0), "res": []}
             for r, dil in ((1, 1), (2, 3), (3, 9)):
                 u = p + f"res_unit{r}."
-                blk["res"].append({"dil": dil, "a1": vec(t(u + "snake1.alpha"), 1.0), "w1": wconv(t(u + "conv1.weight")),
-                                   "b1": vec(t(u + "conv1.bias"), 0.0), "a2": vec(t(u + "snake2.alpha"), 1.0),
-                                   "w2": wconv(t(u + "conv2.weight")), "b2": vec(t(u + "conv2.bias"), 0.0)})
+                blk["res"].append({"dil": dil, "a1": vec(t(u + "snake1.alpha"), 1.0),
+                                   "w1": _wconv16(t(u + "conv1.weight")), "b1": vec(t(u + "conv1.bias"), 0.0),
+                                   "a2": vec(t(u + "snake2.alpha"), 1.0), "w2": _wconv16(t(u + "conv2.weight")),
+                                   "b2": vec(t(u + "conv2.bias"), 0.0)})
             self.blocks.append(blk)
             i += 1
         self.final_alpha = vec(t("encoder.snake1.alpha"), 1.0)
         w2 = t("encoder.conv2.weight")
         self.hidden = w2.shape[0]
-        self.conv2_w, self.conv2_b = wconv(w2), vec(t("encoder.conv2.bias"), 0.0)
+        self.conv2_w, self.conv2_b = _wconv16(w2), vec(t("encoder.conv2.bias"), 0.0)
         self.cd = spec.codebook_dim
         K = spec.n_codebooks
         q = "quantizer.quantizers.{}."
@@ -473,7 +471,7 @@ class HipDacEncoder:
         assert wav.dim() == 3 and wav.shape[1] == 1, "expected [B, 1, T]"
         B, _, T = wav.shape
         assert T % self.hop == 0, f"T={T} must be a multiple of the hop {self.hop} (see preprocess)"
-        dev, P, f16 = self.device, HipDacDecoder._pad32, torch.int16
+        dev, P, f16 = self.device, _pad32, torch.int16
         stream = _lib.stream_ptr(dev)
         wav = wav.to(dev, torch.float32).contiguous()
         C = P(self.c0)
@@ -487,12 +485,9 @@ class HipDacEncoder:
             C = blk["cin"]
             tmp = torch.empty_like(act)
             for j, ru in enumerate(blk["res"]):
-                d = ru["dil"]
                 a_next = blk["res"][j + 1]["a1"] if j + 1 < len(blk["res"]) else blk["alpha"]
-                call("zk_dac_conv_cl", ptr(act), B, C, L, ptr(ru["w1"]), 0, ptr(ru["b1"]), C, 7, d, 3 * d, L,
-                     1, 1, 0, L, None, None, ptr(ru["a2"]), ptr(tmp), 0, None, 1, 1, stream)
-                call("zk_dac_conv_cl", ptr(tmp), B, C, L, ptr(ru["w2"]), 0, ptr(ru["b2"]), C, 1, 1, 0, L,
-                     1, 1, 0, L, ptr(x), ptr(x), ptr(a_next), ptr(act), 0, None, 1, 1, stream)
+                _conv_k7(act, ru["w1"], ru["b1"], ru["dil"], ru["a2"], tmp, None, 1, stream)
+                _conv_1x1_res(tmp, ru["w2"], ru["b2"], x, a_next, act, None, 1, stream)
             del tmp
             st, Co = blk["stride"], blk["cout"]
             Lo = L // st

@@ -519,6 +519,27 @@ bool dac_plan(const zk_dac_desc* d, int B, int T, DacPlan& p) {
     p.total = zk_align(p.last + (size_t)B * L * lastc * 4);
     return true;
 }
+
+// The decoder's three uses of zk_dac_conv_cl (zonos_hip.h). s: fp16 Snake'd activations [B][L][Cin]; every conv
+// applies the next Snake (alpha) in its epilogue; lens counts frames, `scale` samples per frame at this stage.
+// k7 conv, dilated, 'same' padding (the first conv; conv1 of a residual unit): s_out = fp16 Snake(conv + b)
+int dac_conv_k7(const uint16_t* s, int B, int Cin, int L, const uint16_t* w, const float* b, int Cout, int dil,
+                const float* alpha, uint16_t* s_out, const int32_t* lens, int scale, void* stream) {
+    return zk_dac_conv_cl(s, B, Cin, L, w, 0, b, Cout, 7, dil, 3 * dil, L, 1, 1, 0, L, nullptr, nullptr, alpha, s_out, 0,
+                          lens, scale, scale, stream);
+}
+// 1x1 conv + residual (conv2 of a residual unit): x += conv + b, s_out = Snake(x) (s_f32: fp32, for the tail)
+int dac_conv_1x1_res(const uint16_t* s, int B, int C, int L, const uint16_t* w, const float* b, float* x,
+                     const float* alpha, void* s_out, int s_f32, const int32_t* lens, int scale, void* stream) {
+    return zk_dac_conv_cl(s, B, C, L, w, 0, b, C, 1, 1, 0, L, 1, 1, 0, L, x, x, alpha, s_out, s_f32, lens, scale, scale,
+                          stream);
+}
+// ConvTranspose1d(k = 2 st, stride st) as st polyphase 2-tap convs, L -> L st: x = conv + b, s_out = fp16 Snake(x)
+int dac_convt(const uint16_t* s, int B, int Cin, int L, const uint16_t* w, const float* b, int Cout, int st, float* x,
+              const float* alpha, uint16_t* s_out, const int32_t* lens, int scale, void* stream) {
+    return zk_dac_conv_cl(s, B, Cin, L, w, 2L * Cout * Cin, b, Cout, 2, 1, 1, L + 1, st, st, -((st + 1) / 2), L * st,
+                          nullptr, x, alpha, s_out, 0, lens, scale, scale * st, stream);
+}
 }  // namespace
 
 extern "C" size_t zk_dac_decode_workspace(const zk_dac_desc* d, int B, int T) {
@@ -553,8 +574,7 @@ extern "C" int zk_dac_decode(const zk_dac_desc* d, const int64_t* codes, int B, 
     ZK_STEP(zk_dac_rvq_decode_cl(codes, B, d->ncb, T, (long)d->ncb * T, d->tables, d->codebook_size, d->hidden,
                                  d->cin0, z, lens, stream));
     const float* a_next = d->nblocks ? d->blocks[0].alpha : d->final_alpha;
-    ZK_STEP(zk_dac_conv_cl(z, B, d->cin0, T, d->conv1_w, 0, d->conv1_b, d->c0, 7, 1, 3, T, 1, 1, 0, T, nullptr,
-                           nullptr, a_next, bufs[0], 0, lens, 1, 1, stream));
+    ZK_STEP(dac_conv_k7(z, B, d->cin0, T, d->conv1_w, d->conv1_b, d->c0, 1, a_next, bufs[0], lens, 1, stream));
     int L = T, scale = 1, cch = d->c0;
     const void* act = bufs[0];
     bool act_f32 = false;
@@ -562,9 +582,8 @@ extern "C" int zk_dac_decode(const zk_dac_desc* d, const int64_t* codes, int B, 
         const zk_dac_block& k = d->blocks[bi];
         const int st = k.stride, Lo = L * st;
         uint16_t* s_new = other(act, nullptr);
-        ZK_STEP(zk_dac_conv_cl(static_cast<const uint16_t*>(act), B, k.cin, L, k.wt, 2L * k.cout * k.cin, k.bt,
-                               k.cout, 2, 1, 1, L + 1, st, st, -((st + 1) / 2), Lo, nullptr, x, k.res[0].a1, s_new, 0,
-                               lens, scale, scale * st, stream));
+        ZK_STEP(dac_convt(static_cast<const uint16_t*>(act), B, k.cin, L, k.wt, k.bt, k.cout, st, x, k.res[0].a1, s_new,
+                          lens, scale, stream));
         act = s_new;
         scale *= st;
         L = Lo;
@@ -582,12 +601,10 @@ extern "C" int zk_dac_decode(const zk_dac_desc* d, const int64_t* codes, int B, 
                                           ru.a2, ru.w2, ru.b2, x, an, s_out, last ? 1 : 0, lens, scale, stream));
                 act = s_out;
             } else {
-                ZK_STEP(zk_dac_conv_cl(static_cast<const uint16_t*>(act), B, k.cout, L, ru.w1, 0, ru.b1, k.cout, 7,
-                                       ru.dil, 3 * ru.dil, L, 1, 1, 0, L, nullptr, nullptr, ru.a2, tmp, 0, lens,
-                                       scale, scale, stream));
+                ZK_STEP(dac_conv_k7(static_cast<const uint16_t*>(act), B, k.cout, L, ru.w1, ru.b1, k.cout, ru.dil, ru.a2,
+                                    tmp, lens, scale, stream));
                 void* s_out = last ? static_cast<void*>(last_act) : const_cast<void*>(act);
-                ZK_STEP(zk_dac_conv_cl(tmp, B, k.cout, L, ru.w2, 0, ru.b2, k.cout, 1, 1, 0, L, 1, 1, 0, L, x, x, an,
-                                       s_out, last ? 1 : 0, lens, scale, scale, stream));
+                ZK_STEP(dac_conv_1x1_res(tmp, B, k.cout, L, ru.w2, ru.b2, x, an, s_out, last ? 1 : 0, lens, scale, stream));
                 act = s_out;
             }
             if (last) act_f32 = true;

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include "warm.h"
 
 #define ZK_DEV __device__ __forceinline__
@@ -233,3 +234,13 @@ extern "C" void zk_set_error(const char* fmt, ...);
         const int _rc = (expr);     \
         if (_rc != 0) return _rc;   \
     } while (0)
+
+// ---------------------------------------------------------------- run-time value -> template constant
+// pick(f, v1, Ints<...>{}, v2, Ints<...>{}, ...) calls f(std::integral_constant<int, V1>{}, ...) for the
+// listed constants equal to the run-time values v1, v2, ...; false when a value is not listed
+template <int... Vs> struct Ints {};
+template <class F> bool pick(F&& f) { return f(), true; }
+template <class F, int... Vs, class... More>
+bool pick(F&& f, int v, Ints<Vs...>, More... more) {
+    return ((v == Vs && pick([&](auto... rest) { f(std::integral_constant<int, Vs>{}, rest...); }, more...)) || ...);
+}

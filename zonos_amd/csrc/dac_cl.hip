@@ -32,7 +32,6 @@ namespace {
 typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 
-constexpr int QT = 128;          // positions per workgroup (NQ = 4)
 constexpr int MAXSPAN = 64;      // max (ks-1)*dil
 
 __device__ __attribute__((aligned(256))) uint4 g_zero_page[16];   // 256 zero bytes (LDS-DMA source for padding)
@@ -97,12 +96,10 @@ __device__ uint32_t g_clhw[4096][8];       // every workgroup < 4096: HW_ID of w
 #define ZK_CL_STAMP(role, st) do { } while (0)
 #endif
 constexpr int CL_DA = ZK_CL_DA;          // weight slices in flight ahead of the step being computed
-constexpr int CL_NW = CL_DA + 2;         // weight ring slots
 #ifndef ZK_CL_NLD
 #define ZK_CL_NLD 2
 #endif
 constexpr int CL_NLD = ZK_CL_NLD;        // loader waves (LDS-DMA issue is the per-step limit with one)
-constexpr int CL_THREADS = 256 + 64 * CL_NLD;   // 4 compute waves + the loaders
 
 // Loader-wave implicit GEMM, persistent. Waves 4.. only move bytes (LDS-DMA) and count their own
 // vmcnt; waves 0-3 only read LDS + MFMA, so the vmcnt(0) that hipcc places before their ds_reads
@@ -127,28 +124,68 @@ constexpr int RU_XPD = 4;            // fused unit: residual output blocks in fl
 // multiplies them in registers against the C x C weights staged once in LDS, adds the residual
 // and writes x and the next Snake: the fp16 intermediate never goes to HBM (4 of the unit's 16 B
 // per element) and the 1x1 conv's launch, rings and barriers are gone.
-template <int FM, bool SF32, bool RES, int NQ, int DA = CL_DA, int OCC = 2, int NWY = 2, int NLDK = CL_NLD,
-          int NWM = 2, bool FUSE = false>
-__global__ __launch_bounds__(64 * (NWM * NWY + NLDK), (OCC * 64 * (NWM * NWY + NLDK) + 255) / 256) void k_conv_cl(
+//
+// The workgroup shapes. S carries NQ (16-position blocks per wave), DA, OCC, NWY, NLDK, NWM, FUSE and what
+// follows from them; FMF is the one FM a fused shape is built for (C / 16), 0 = any.
+template <int NQ_, int DA_, int OCC_, int NWY_, int NLDK_, int NWM_, bool FUSE_, int FMF_ = 0>
+struct ConvShape {
+    static constexpr int NQ = NQ_, DA = DA_, OCC = OCC_, NWY = NWY_, NLDK = NLDK_, NWM = NWM_, FMF = FMF_;
+    static constexpr bool FUSE = FUSE_;
+    static constexpr int THREADS = 64 * (NWM * NWY + NLDK);
+    static constexpr int QTT = 16 * NQ * NWY;                     // positions per tile
+    static constexpr int co_t(int fm) { return 16 * fm * NWM; }   // channels per tile
+    // fused: the 1x1 weights as an LDS image (row stride co_t + 8 halves) when one workgroup per CU has
+    // room for it (C = 96), else read per output block from L1 / L2, one block ahead
+    static constexpr bool w1lds(int fm) { return FUSE && OCC == 1 && co_t(fm) * (co_t(fm) + 8) * 2 <= 24 * 1024; }
+};
+using ShapePair = ConvShape<4, CL_DA, 2, 2, CL_NLD, 2, false>;   // two per CU: 4 compute waves, 128 positions
+using ShapeFat = ConvShape<8, CL_DA, 1, 4, 4, 2, false>;         // one per CU: 8 compute waves, 512 positions
+using ShapeFused96 = ConvShape<4, CL_DA, 1, 8, 4, 1, true, 6>;   // fused unit, C = 96: 8 position waves, 512 positions
+using ShapeFused192 = ConvShape<2, CL_DA, 1, 8, 4, 1, true, 12>; // fused unit, C = 192: 256 positions
+
+// The dynamic LDS of k_conv_cl<S, FM>, in bytes:
+// [weight ring: DA + 2 slots][window ring: nx slots of xs][epilogue tables x 2 (tile parity)][fused: 1x1 image].
+// The kernel takes its pointers from it, the host (conv_plan) its byte count.
+struct ConvLds {
+    int ws, nws, ept, w1;         // weight slot, weight ring slots, one epilogue table, 1x1 weight image
+    static constexpr int pieces(int win) { return (win + 15) >> 4; }         // window slot: 16-row pieces
+    static constexpr int xs(int nxp) { return nxp * 1024; }                  // ... of 1 KiB
+    // from base = the kernel's LDS pointer, or 0 for plain offsets
+    template <class P> constexpr P xring(P base) const { return base + nws * ws; }
+    template <class P> constexpr P tables(P base, int nx, int xs_) const { return xring(base) + nx * xs_; }
+    template <class P> constexpr P w1img(P base, int nx, int xs_) const { return tables(base, nx, xs_) + 2 * ept; }
+    constexpr int bytes(int nx, int xs_) const { return w1img(0, nx, xs_) + w1; }
+};
+template <class S>
+constexpr ConvLds conv_lds(int fm) {
+    const int co_t = S::co_t(fm);
+    return ConvLds{co_t * 64, S::DA + 2, (S::FUSE ? 6 : 3) * co_t * (int)sizeof(float),
+                   S::w1lds(fm) ? co_t * (co_t + 8) * 2 : 0};
+}
+
+template <class S, int FM, bool SF32, bool RES>
+__global__ __launch_bounds__(S::THREADS, (S::OCC * S::THREADS + 255) / 256) void k_conv_cl(
     const uint16_t* __restrict__ in, int Cin, int Tin, const uint16_t* __restrict__ w, long wphase,
     const float* __restrict__ bias, int Cout, int ks, int dil, int pad, int Qn, int nphase, int out_stride,
     int out_off0, int Tout, const float* resid, float* xout, const float* __restrict__ alpha,
     void* __restrict__ sout, int s_f32, const int32_t* __restrict__ lens, int in_scale, int out_scale, int nq,
     int nx_slots, int dx, int B, const uint16_t* __restrict__ w1x1, const float* __restrict__ b1x1,
     const float* __restrict__ alpha_out) {
+    constexpr int NQ = S::NQ, DA = S::DA, NWY = S::NWY, NLDK = S::NLDK, NWM = S::NWM;
+    constexpr bool FUSE = S::FUSE;
+    constexpr ConvLds LDS = conv_lds<S>(FM);
     constexpr int CI = 32;
     using I = Img<CI>;
-    constexpr int CO_T = 16 * FM * NWM;
-    constexpr int WS = CO_T * I::RB;             // weight slot bytes
+    constexpr int CO_T = S::co_t(FM);
+    constexpr int WS = LDS.ws;                   // weight slot bytes (CO_T rows of CI halves)
+    static_assert(WS == CO_T * I::RB, "weight slot = CO_T image rows");
     constexpr int NWP = CO_T / 16;               // weight pieces (1 KiB = 16 rows) per step
     constexpr int NCW = NWM * NWY;               // compute waves
     static_assert(!FUSE || (NWM == 1 && !RES), "fused residual unit: one channel wave, residual in the epilogue");
     constexpr int W1S = CO_T + 8;                // fused: 1x1 weight image row stride (halves)
-    // fused: the 1x1 weights as an LDS image when one workgroup per CU has room for it (C = 96), else
-    // read per output block from L1 / L2, one block ahead
-    constexpr bool W1LDS = FUSE && OCC == 1 && CO_T * W1S * 2 <= 24 * 1024;
-    constexpr int QTT = 16 * NQ * NWY;           // positions per tile
-    extern __shared__ __attribute__((aligned(16))) char smem[];   // [W ring][X ring][epilogue tables x 2]
+    constexpr bool W1LDS = S::w1lds(FM);
+    constexpr int QTT = S::QTT;                  // positions per tile
+    extern __shared__ __attribute__((aligned(16))) char smem[];   // laid out by ConvLds
 
     // Tiles: XCD x (= blockIdx.x % 8 under round-robin dispatch) owns the contiguous range [lo, hi)
     // of the tile order (channel tile fastest, then position tile, then row), and its
@@ -170,13 +207,13 @@ __global__ __launch_bounds__(64 * (NWM * NWY + NLDK), (OCC * 64 * (NWM * NWY + N
 
     const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int win = QTT + (ks - 1) * dil;
-    const int nxp = (win + 15) >> 4;             // window pieces (16 rows each)
-    const int XS = nxp * 1024;
+    const int nxp = ConvLds::pieces(win);        // window pieces (16 rows each)
+    const int XS = ConvLds::xs(nxp);
     // weight ring slots: the loader refills a slot at most 2 steps after the barrier that let it
     // run (it can be one step ahead of the barrier it passed, the compute waves one behind it)
-    constexpr int NWS = DA + 2;
+    constexpr int NWS = LDS.nws;
     char* const wring = smem;
-    char* const xring = smem + NWS * WS;
+    char* const xring = LDS.xring(smem);
     const int nchunk = Cin / CI, nstep = nchunk * ks;
 
 #ifdef ZK_CL_PROF
@@ -307,9 +344,10 @@ __global__ __launch_bounds__(64 * (NWM * NWY + NLDK), (OCC * 64 * (NWM * NWY + N
     const int ln = lane & 15, lg = lane >> 4, wm = wv / NWY, wn = wv % NWY;
     int t = 0, xslot = 0, wslot = 0;             // tap, window ring slot, weight ring slot of the step
     constexpr int NE = FUSE ? 6 : 3;             // epilogue constant tables per tile
+    static_assert(LDS.ept == NE * CO_T * (int)sizeof(float), "epilogue table = NE rows of CO_T floats");
     // fused: the 1x1 weights [co][ci] as an LDS image (row stride W1S halves), staged once per
     // workgroup; visible to every compute wave after the first step barrier
-    uint16_t* const w1img = reinterpret_cast<uint16_t*>(xring + nx_slots * XS + 2 * NE * CO_T * sizeof(float));
+    uint16_t* const w1img = reinterpret_cast<uint16_t*>(LDS.w1img(smem, nx_slots, XS));
     if constexpr (W1LDS) {
         for (int i = tid; i < CO_T * CO_T / 8; i += 64 * NCW) {
             const int row = i / (CO_T / 8), c8 = i % (CO_T / 8);
@@ -330,7 +368,7 @@ __global__ __launch_bounds__(64 * (NWM * NWY + NLDK), (OCC * 64 * (NWM * NWY + N
         // staged into an LDS table (two, by tile parity: a wave may still read the previous tile's)
         // while the steps run (the epilogue used to start with their global loads and four IEEE
         // divisions per channel quartet)
-        float* const ept = reinterpret_cast<float*>(xring + nx_slots * XS) + (it & 1) * NE * CO_T;
+        float* const ept = reinterpret_cast<float*>(LDS.tables(smem, nx_slots, XS)) + (it & 1) * NE * CO_T;
         for (int i = tid; i < CO_T; i += 64 * NCW) {
             const float a_ = (FUSE || sout) ? alpha[co0 + i] : 1.f;
             ept[i] = bias[co0 + i];
@@ -767,79 +805,112 @@ __global__ __launch_bounds__(256) void k_rvq_encode(const float* __restrict__ z,
     }
 }
 
-// Persistent grid: as many workgroups as are resident at once (occupancy query for this kernel and
-// LDS size x CUs), a multiple of 8 (the kernel's XCD split), at most one per tile.
-template <int FM, int NQ, int NWY = 2, int NLDK = CL_NLD, int DA = CL_DA, int OCC = 2>
-int launch_conv(long ntiles, size_t lds, hipStream_t st, const uint16_t* in, int B, int Cin, int Tin,
-                const uint16_t* w, long wphase, const float* bias, int Cout, int ks, int dil, int pad, int Qn,
-                int nphase, int out_stride, int out_off0, int Tout, const float* resid, float* xout,
-                const float* alpha, void* sout, int s_f32, const int32_t* lens, int in_scale, int out_scale, int nq,
-                int nx, int dx) {
-    constexpr int NT = 64 * (2 * NWY + NLDK);
-    auto kern = &k_conv_cl<FM, false, false, NQ, DA, OCC, NWY, NLDK>;     // NQ = 8: fp16 output, no residual only
-    if constexpr (NQ == 4 && DA == CL_DA && NWY == 2)
-        kern = resid ? (s_f32 ? &k_conv_cl<FM, true, true, NQ> : &k_conv_cl<FM, false, true, NQ>)
-                     : (s_f32 ? &k_conv_cl<FM, true, false, NQ> : kern);
-    if (lds > 65536)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)lds);
-    // the current device's CU count (queried per call: a process may drive several devices)
-    int dev = 0, ncu = 0;
-    ZK_HIP(hipGetDevice(&dev));
-    ZK_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-    int occ = 0;
-    ZK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, reinterpret_cast<const void*>(kern), NT, lds));
-    ZK_REQUIRE(occ >= 1, "zk_dac_conv_cl: kernel does not fit a CU (LDS %zu)", lds);
-    const long resident = (long)ncu * occ / 8 * 8;
-    const long grid = std::min<long>((ntiles + 7) / 8 * 8, std::max<long>(resident, 8));
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NT), lds, st, in, Cin, Tin, w, wphase, bias, Cout, ks,
-                       dil, pad, Qn, nphase, out_stride, out_off0, Tout, resid, xout, alpha, sout, s_f32, lens,
-                       in_scale, out_scale, nq, nx, dx, B, nullptr, nullptr, nullptr);
-    return 0;
+// ---------------------------------------------------------------- conv launch plan
+enum { SHAPE_PAIR = 0, SHAPE_FAT = 1, SHAPE_FUSED96 = 2, SHAPE_FUSED192 = 3 };
+template <class F>
+auto with_shape(int shape, F&& f) {
+    return shape == SHAPE_FAT ? f(ShapeFat{}) : shape == SHAPE_FUSED96 ? f(ShapeFused96{})
+         : shape == SHAPE_FUSED192 ? f(ShapeFused192{}) : f(ShapePair{});
+}
+struct ConvPlan { int shape, fm, qt, dx, nx, lds, nq, tiles, occ; };     // zk_dac_conv_plan's array (zonos_hip.h)
+
+// The launch of a conv, from its shape alone (no GPU). fused: the residual unit of C = Cout channels over
+// Qn = T positions (k7, one phase; Cin, ks, nphase, resid are not read).
+int conv_plan(const char* name, bool fused, int B, int Cin, int Cout, int ks, int dil, int Qn, int nphase, bool resid,
+              bool s_f32, ConvPlan& p) {
+    if (fused) {
+        // C = 96: one workgroup per CU of 8 position waves + 4 loaders, the 1x1 weights in LDS (two per CU of 4 + 2
+        // waves, the weights read through L1, measured slower: DESIGN.md §6 round 4). C = 192: the same waves on
+        // 256-position tiles, the 1x1 weights (72 KB) read from L2 one output block ahead.
+        ZK_REQUIRE(Cout == 96 || Cout == 192, "%s: C=%d (the fused unit is built for C = 96 and 192)", name, Cout);
+        ZK_REQUIRE(dil >= 1 && 6 * dil <= MAXSPAN, "%s: dil=%d", name, dil);
+        ks = 7, nphase = 1;
+        p.shape = Cout == 96 ? SHAPE_FUSED96 : SHAPE_FUSED192, p.fm = Cout / 16;
+    } else {
+        ZK_REQUIRE(Cin > 0 && Cin % 32 == 0, "%s: Cin=%d must be a multiple of 32", name, Cin);
+        ZK_REQUIRE(Cout > 0 && Cout % 32 == 0, "%s: Cout=%d must be a multiple of 32", name, Cout);
+        ZK_REQUIRE(ks >= 1 && ks <= 7 && dil >= 1 && (ks - 1) * dil <= MAXSPAN, "%s: ks=%d dil=%d", name, ks, dil);
+        ZK_REQUIRE(nphase >= 1, "%s: bad arguments", name);
+        const int nco = Cout / 32;
+        p.fm = nco % 4 == 0 ? 4 : (nco % 3 == 0 ? 3 : (nco % 2 == 0 ? 2 : 1));
+        // Wider tiles for the plain convs without a residual at FM <= 3 (the 96-192-channel k7 convs,
+        // overhead-bound at 128 positions: -6 % / -15 % at 256); the residual convs keep 128 (their
+        // prefetched residual tile would not fit the registers beside twice the accumulators), and so do
+        // the polyphase ConvTranspose convs (+12-22 % with 256, profiles/r1_dac_wide_tiles_ab.txt)
+        // (one workgroup per CU with a deeper weight ring measured slower: DESIGN.md §6)
+        // fat: those convs as ONE workgroup per CU of 8 compute waves (2 channel halves x 4 position
+        // quarters, 512-position tiles) + 4 loaders = 12 waves, exactly 3 per SIMD. Two 6-wave
+        // workgroups per CU of 256-position tiles (the same compute per step) were co-resident only where the wave placement
+        // happened to balance the SIMDs (3 waves per SIMD is the register limit at 150 VGPRs): 1.3 per CU
+        // on average (tools/dac_conv_stamps.py HW_ID census); one workgroup also shares each weight slice
+        // among twice the waves.
+        p.shape = (!resid && !s_f32 && nphase == 1 && p.fm <= 3) ? SHAPE_FAT : SHAPE_PAIR;
+    }
+    return with_shape(p.shape, [&](auto shape) -> int {
+        using S = decltype(shape);
+        const ConvLds lay = conv_lds<S>(p.fm);
+        const int xs = ConvLds::xs(ConvLds::pieces(S::QTT + (ks - 1) * dil));
+        // window lead dx >= DA steps, window ring nx = 1 + ceil((dx + 1) / ks) slots; the lead shrinks until
+        // OCC workgroups fit a CU's 160 KiB of LDS. (A 1x1 conv starts at dx = DA, so nothing shrinks: nx = 5,
+        // and at FM = 4 the pair shape takes 84,992 B -- one workgroup per CU. DESIGN.md, open items.)
+        const int cap = 160 * 1024 / S::OCC;
+        for (p.dx = std::max(S::DA, ks);; --p.dx) {
+            p.nx = 1 + (p.dx + ks) / ks, p.lds = lay.bytes(p.nx, xs);
+            if (p.dx <= S::DA || p.lds <= cap) break;
+        }
+        ZK_REQUIRE(p.lds <= 160 * 1024, "%s: LDS %d too large (Cout %d ks %d dil %d)", name, p.lds, Cout, ks, dil);
+        p.qt = S::QTT, p.occ = S::OCC;
+        p.nq = Qn > 0 ? (Qn + S::QTT - 1) / S::QTT : 0;
+        const long tiles = (long)B * p.nq * (Cout / S::co_t(p.fm)) * nphase;
+        ZK_REQUIRE(tiles < (1L << 31), "%s: too many tiles", name);
+        p.tiles = (int)tiles;
+        return 0;
+    });
 }
 
-// The fused residual unit: position waves each holding all C channels (C = 96: 64 positions,
-// FM = 6, NQ = 4; C = 192: 32 positions, FM = 12, NQ = 2), persistent like launch_conv.
-// C = 96: one workgroup per CU of 8 position waves + 4 loaders, the 1x1 weights in LDS (two workgroups
-// per CU of 4 position waves + 2 loaders, the weights read through L1, measured slower: DESIGN.md §6
-// round 4). C = 192: one workgroup per CU of 8 position waves (256-position tiles) + 4 loaders, the
-// 1x1 weights (72 KB) read from L2 one output block ahead.
-template <int C_, bool SF32>
-int launch_resunit(const uint16_t* s_in, int B, int T, const uint16_t* w7, const float* b7, int dil, const float* a2,
-                   const uint16_t* w1, const float* b1, float* x, const float* alpha_next, void* s_out,
-                   const int32_t* lens, int scale, hipStream_t st) {
-    constexpr int FM = C_ / 16, NQ = C_ == 96 ? 4 : 2, NWY = 8, NLD = 4;
-    constexpr int NT = 64 * (NWY + NLD);
-    constexpr int qt = 16 * NQ * NWY;
-    constexpr bool w1lds = C_ * (C_ + 8) * 2 <= 24 * 1024;     // = the kernel's W1LDS
-    auto kern = &k_conv_cl<FM, SF32, false, NQ, CL_DA, 1, NWY, NLD, 1, true>;
-    const int ks = 7, win = qt + (ks - 1) * dil;
-    const size_t xs = (size_t)((win + 15) / 16) * 1024, ws = (size_t)C_ * 64;
-    const size_t fixed = (size_t)2 * 6 * C_ * sizeof(float) + (w1lds ? (size_t)C_ * (C_ + 8) * 2 : 0);
-    const size_t cap = 160 * 1024;
-    const int nws = CL_DA + 2;
-    int dx = std::max(CL_DA, ks), nx = 1 + (dx + ks) / ks;
-    while (dx > CL_DA && nws * ws + nx * xs + fixed > cap) {
-        --dx;
-        nx = 1 + (dx + ks) / ks;
-    }
-    const size_t lds = nws * ws + nx * xs + fixed;
-    ZK_REQUIRE(lds <= cap, "zk_dac_resunit_cl: LDS %zu too large (C %d dil %d)", lds, C_, dil);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+// the instantiations: pair FM 1-4 x Snake output x residual, fat FM 1-3 (fp16 Snake, no residual), the
+// fused units x Snake output (their residual is added in the fused epilogue: RES = false)
+template <class S>
+constexpr bool conv_has(int fm, bool sf32, bool res) {
+    return S::FUSE ? (fm == S::FMF && !res) : S::OCC == 1 ? (fm <= 3 && !sf32 && !res) : fm <= 4;
+}
+
+// Persistent grid: as many workgroups as are resident at once (occupancy query for this kernel and
+// LDS size x CUs), a multiple of 8 (the kernel's XCD split), at most one per tile.
+template <class K, class... A>
+int conv_launch_kernel(K kern, int threads, const ConvPlan& p, const char* name, hipStream_t st, A... args) {
+    const size_t lds = (size_t)p.lds;
+    const void* fn = reinterpret_cast<const void*>(kern);
+    if (lds > 65536) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    // the current device's CU count (queried per call: a process may drive several devices)
     int dev = 0, ncu = 0, occ = 0;
     ZK_HIP(hipGetDevice(&dev));
     ZK_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-    ZK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, reinterpret_cast<const void*>(kern), NT, lds));
-    ZK_REQUIRE(occ >= 1, "zk_dac_resunit_cl: kernel does not fit a CU (LDS %zu)", lds);
-    const int nq = (T + qt - 1) / qt;
-    const long ntiles = (long)B * nq;
-    ZK_REQUIRE(ntiles < (1L << 31), "zk_dac_resunit_cl: too many tiles");
+    ZK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, threads, lds));
+    ZK_REQUIRE(occ >= 1, "%s: kernel does not fit a CU (LDS %zu)", name, lds);
     const long resident = (long)ncu * occ / 8 * 8;
-    const long grid = std::min<long>((ntiles + 7) / 8 * 8, std::max<long>(resident, 8));
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NT), lds, st, s_in, C_, T, w7, 0L, b7, C_, ks, dil,
-                       3 * dil, T, 1, 1, 0, T, x, x, a2, s_out, (int)SF32, lens, scale, scale, nq, nx, dx, B, w1, b1,
-                       alpha_next);
+    const long grid = std::min<long>(((long)p.tiles + 7) / 8 * 8, std::max<long>(resident, 8));
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(threads), lds, st, args...);
+    ZK_CHECK_LAUNCH(name);
     return 0;
+}
+
+// args: k_conv_cl's whole argument list (RES = a residual read by the plain epilogue)
+template <class... A>
+int conv_launch(const ConvPlan& p, bool sf32, bool res, const char* name, hipStream_t st, A... args) {
+    int rc = 0;
+    bool launched = false;
+    with_shape(p.shape, [&](auto shape) {
+        using S = decltype(shape);
+        return pick([&](auto fm, auto f32, auto r) {
+            if constexpr (conv_has<S>(fm(), f32(), r())) {
+                rc = conv_launch_kernel(&k_conv_cl<S, fm(), f32() != 0, r() != 0>, S::THREADS, p, name, st, args...);
+                launched = true;
+            }
+        }, p.fm, Ints<1, 2, 3, 4, 6, 12>{}, (int)sf32, Ints<0, 1>{}, (int)res, Ints<0, 1>{});
+    });
+    ZK_REQUIRE(launched, "%s: no kernel for the plan (shape %d FM %d)", name, p.shape, p.fm);
+    return rc;
 }
 
 }  // namespace
@@ -885,65 +956,27 @@ extern "C" int zk_dac_conv_cl(const uint16_t* in, int B, int Cin, int Tin, const
                               int out_stride, int out_off0, int Tout, const float* resid, float* x_out,
                               const float* alpha_next, void* s_out, int s_f32, const int32_t* lens, int in_scale,
                               int out_scale, void* stream) {
-    ZK_REQUIRE(Cin > 0 && Cin % 32 == 0, "zk_dac_conv_cl: Cin=%d must be a multiple of 32", Cin);
-    ZK_REQUIRE(Cout > 0 && Cout % 32 == 0, "zk_dac_conv_cl: Cout=%d must be a multiple of 32", Cout);
-    ZK_REQUIRE(ks >= 1 && ks <= 7 && dil >= 1 && (ks - 1) * dil <= MAXSPAN, "zk_dac_conv_cl: ks=%d dil=%d", ks, dil);
-    ZK_REQUIRE(nphase >= 1 && bias != nullptr && (s_out == nullptr || alpha_next != nullptr) &&
-                   (s_out != nullptr || x_out != nullptr),
+    const char* const name = "zk_dac_conv_cl";
+    ConvPlan p;
+    ZK_TRY(conv_plan(name, false, B, Cin, Cout, ks, dil, Qn, nphase, resid != nullptr, s_f32 != 0, p));
+    ZK_REQUIRE(bias != nullptr && (s_out == nullptr || alpha_next != nullptr) && (s_out != nullptr || x_out != nullptr),
                "zk_dac_conv_cl: bad arguments");
     if (B == 0 || Qn <= 0) return 0;
-    const int nco = Cout / 32;
-    const int FM = nco % 4 == 0 ? 4 : (nco % 3 == 0 ? 3 : (nco % 2 == 0 ? 2 : 1));
-    // Wider tiles for the plain convs without a residual at FM <= 3 (the 96-192-channel k7 convs,
-    // overhead-bound at 128 positions: -6 % / -15 % at 256); the residual convs keep 128 (their
-    // prefetched residual tile would not fit the registers beside twice the accumulators), and so do
-    // the polyphase ConvTranspose convs (+12-22 % with 256, profiles/r1_dac_wide_tiles_ab.txt)
-    // (one workgroup per CU with a deeper weight ring measured slower: DESIGN.md §6)
-    // fat: those convs as ONE workgroup per CU of 8 compute waves (2 channel halves x 4 position
-    // quarters, 512-position tiles) + 4 loaders = 12 waves, exactly 3 per SIMD. Two 6-wave
-    // workgroups per CU of 256-position tiles (the same compute per step) were co-resident only where the wave placement
-    // happened to balance the SIMDs (3 waves per SIMD is the register limit at 150 VGPRs): 1.3 per CU
-    // on average (tools/dac_conv_stamps.py HW_ID census); one workgroup also shares each weight slice
-    // among twice the waves.
-    const bool fat = resid == nullptr && !s_f32 && nphase == 1 && FM <= 3;
-    const int qt = fat ? 4 * QT : QT;
-    const int win = qt + (ks - 1) * dil;
-    const size_t xs = (size_t)((win + 15) / 16) * 1024;
-    const size_t ws = (size_t)32 * FM * 64;
-    const int da = CL_DA;
-    const size_t lds_cap = fat ? 160 * 1024 : 80 * 1024;
-    // window lead DX >= da steps, ring NX = 1 + ceil((DX + 1)/ks) slots, weight ring da + 2;
-    // keep LDS <= 80 KiB (2 per CU)
-    const size_t ept = (size_t)2 * 3 * 32 * FM * sizeof(float);      // epilogue constants tables (x 2)
-    const int nws = da + 2;
-    int dx = std::max(da, ks), nx = 1 + (dx + ks) / ks;
-    while (dx > da && nws * ws + nx * xs + ept > lds_cap) {
-        --dx;
-        nx = 1 + (dx + ks) / ks;
-    }
-    const size_t lds = nws * ws + nx * xs + ept;
-    ZK_REQUIRE(lds <= 160 * 1024, "zk_dac_conv_cl: LDS %zu too large", lds);
-    const int nq = (Qn + qt - 1) / qt;
-    const long ntiles = (long)B * nq * (Cout / (32 * FM)) * nphase;
-    ZK_REQUIRE(ntiles < (1L << 31), "zk_dac_conv_cl: too many tiles");
-    hipStream_t st = (hipStream_t)stream;
-#define ZK_CL(F_, NQ_)                                                                                           \
-    ZK_TRY((launch_conv<F_, NQ_>(ntiles, lds, st, in, B, Cin, Tin, w, w_phase_stride, bias, Cout, ks, dil, pad, Qn,  \
-                                 nphase, out_stride, out_off0, Tout, resid, x_out, alpha_next, s_out, s_f32, lens,   \
-                                 in_scale, out_scale, nq, nx, dx)))
-#define ZK_CLF(F_)                                                                                                \
-    ZK_TRY((launch_conv<F_, 8, 4, 4, CL_DA, 1>(ntiles, lds, st, in, B, Cin, Tin, w, w_phase_stride, bias, Cout, ks, dil, \
-                                     pad, Qn, nphase, out_stride, out_off0, Tout, resid, x_out, alpha_next, s_out,    \
-                                     s_f32, lens, in_scale, out_scale, nq, nx, dx)))
-    switch (FM) {
-        case 4: ZK_CL(4, 4); break;
-        case 3: if (fat) ZK_CLF(3); else ZK_CL(3, 4); break;
-        case 2: if (fat) ZK_CLF(2); else ZK_CL(2, 4); break;
-        default: if (fat) ZK_CLF(1); else ZK_CL(1, 4); break;
-    }
-#undef ZK_CLF
-#undef ZK_CL
-    ZK_CHECK_LAUNCH("zk_dac_conv_cl");
+    return conv_launch(p, s_f32 != 0, resid != nullptr, name, (hipStream_t)stream, in, Cin, Tin, w, w_phase_stride, bias,
+                       Cout, ks, dil, pad, Qn, nphase, out_stride, out_off0, Tout, resid, x_out, alpha_next, s_out, s_f32,
+                       lens, in_scale, out_scale, p.nq, p.nx, p.dx, B, nullptr, nullptr, nullptr);
+}
+
+// The plan of zk_dac_conv_cl (fused = 0) or zk_dac_resunit_cl (fused = 1) for a shape, by the entries' own
+// checks and rule; touches no GPU.
+extern "C" int zk_dac_conv_plan(int fused, int B, int Cin, int Cout, int ks, int dil, int Qn, int nphase, int resid,
+                                int s_f32, int32_t* plan) {
+    ConvPlan p;
+    ZK_REQUIRE(plan != nullptr, "zk_dac_conv_plan: null plan");
+    if (conv_plan("zk_dac_conv_plan", fused != 0, B, Cin, Cout, ks, dil, Qn, nphase, resid != 0, s_f32 != 0, p) != 0)
+        return -1;
+    const int32_t v[ZK_DAC_PLAN_N] = {p.shape, p.fm, p.qt, p.dx, p.nx, p.lds, p.nq, p.tiles, p.occ};
+    std::copy(v, v + ZK_DAC_PLAN_N, plan);
     return 0;
 }
 
@@ -956,20 +989,18 @@ extern "C" int zk_dac_resunit_cl(const uint16_t* s_in, int B, int C, int T, cons
                                  int dil, const float* a2, const uint16_t* w1, const float* b1, float* x,
                                  const float* alpha_next, void* s_out, int s_f32, const int32_t* lens, int scale,
                                  void* stream) {
-    ZK_REQUIRE(C == 96 || C == 192, "zk_dac_resunit_cl: C=%d (the fused unit is built for C = 96 and 192)", C);
-    ZK_REQUIRE(dil >= 1 && 6 * dil <= MAXSPAN, "zk_dac_resunit_cl: dil=%d", dil);
+    const char* const name = "zk_dac_resunit_cl";
+    ConvPlan p;
+    ZK_TRY(conv_plan(name, true, B, C, C, 7, dil, T, 1, false, s_f32 != 0, p));
     ZK_REQUIRE(s_in != nullptr && w7 && b7 && a2 && w1 && b1 && x && alpha_next && s_out,
                "zk_dac_resunit_cl: null argument");
     ZK_REQUIRE(s_out != static_cast<const void*>(s_in),
                "zk_dac_resunit_cl: s_out must not alias s_in (neighbouring tiles read it as their halo)");
     if (B == 0 || T <= 0) return 0;
-    hipStream_t st = (hipStream_t)stream;
-#define ZK_RU(C_, F_) ZK_TRY((launch_resunit<C_, F_>(s_in, B, T, w7, b7, dil, a2, w1, b1, x, alpha_next, s_out, lens, scale, st)))
-    if (C == 96) { if (s_f32) ZK_RU(96, true); else ZK_RU(96, false); }
-    else { if (s_f32) ZK_RU(192, true); else ZK_RU(192, false); }
-#undef ZK_RU
-    ZK_CHECK_LAUNCH("zk_dac_resunit_cl");
-    return 0;
+    // the k7 conv's arguments, the residual x in and out; the 1x1 conv and the next Snake behind them
+    return conv_launch(p, s_f32 != 0, false, name, (hipStream_t)stream, s_in, C, T, w7, 0L, b7, C, 7, dil, 3 * dil, T, 1,
+                       1, 0, T, x, x, a2, s_out, (int)(s_f32 != 0), lens, scale, scale, p.nq, p.nx, p.dx, B, w1, b1,
+                       alpha_next);
 }
 
 #ifdef ZK_CL_PROF

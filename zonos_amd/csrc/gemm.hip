@@ -1092,14 +1092,6 @@ int zk_gemm_pf(const void* A, long lda, const void* W, int M, int N, int K, int 
 
 namespace {
 
-// pick(f, v1, Ints<...>{}, v2, Ints<...>{}, ...) calls f(std::integral_constant<int, V1>{}, ...) for the
-// listed constants equal to the run-time values v1, v2, ...; false when a value is not listed
-template <int... Vs> struct Ints {};
-template <class F> bool pick(F&& f) { return f(), true; }
-template <class F, int... Vs, class... More>
-bool pick(F&& f, int v, Ints<Vs...>, More... more) {
-    return ((v == Vs && pick([&](auto... rest) { f(std::integral_constant<int, Vs>{}, rest...); }, more...)) || ...);
-}
 constexpr bool one_of(int v, std::initializer_list<int> list) {
     for (int x : list)
         if (x == v) return true;
