@@ -256,7 +256,7 @@ def test_attention_decode(R, ctx, H, Hk, nsplit):
     hd = 128
     smax = ((ctx + 255) // 256) * 256
     k, v, kc, vt = _attn_setup(R, ctx, H, Hk, hd, smax)
-    q = torch.randn(R, 1, H, hd).to(torch.bfloat16)
+    q = torch.randn(R, 1, H, hd, generator=torch.Generator().manual_seed(ctx + 1)).to(torch.bfloat16)
     ref = F.scaled_dot_product_attention(q.transpose(1, 2).float(), k.transpose(1, 2).float(),
                                          v.transpose(1, 2).float(), enable_gqa=True).transpose(1, 2).reshape(R, H * hd)
     nsplit = min(nsplit, smax // 128)
@@ -472,7 +472,8 @@ def test_attention_out_proj_merge(R, ctx, nsplit):
     part = (torch.randn(R * (H + 2 * Hk) * hd, generator=g) * 0.5).to(DEV)
     freqs = rope_table(16384, hd).to(DEV)
     s = stream_ptr()
-    Wo = pack_weights((torch.randn(D, H * hd, generator=g) * 0.02).to(torch.bfloat16).to(DEV), s)
+    Wo_ = (torch.randn(D, H * hd, generator=g) * 0.02).to(torch.bfloat16)
+    Wo = pack_weights(Wo_.to(DEV), s)
     x0 = torch.randn(R, D, generator=g).to(torch.bfloat16).to(DEV)
     # reference sequence: attention output (split + combine launch), then out_proj + residual
     kc1, vt1, x1 = kc.clone(), vt.clone(), x0.clone()
@@ -490,8 +491,21 @@ def test_attention_out_proj_merge(R, ctx, nsplit):
     torch.cuda.synchronize()
     assert torch.equal(kc1, kc2) and torch.equal(vt1, vt2)
     assert torch.equal(x1.view(torch.int16), x2.view(torch.int16)), (x1.float() - x2.float()).abs().max()
-    # and the result is the attention + projection of an fp32 reference within bf16 tolerance
+    # and the result is the attention + projection of an fp32 reference within bf16 tolerance: x0 +
+    # bf16(SDPA in fp32 over the cache as the launch left it, q from zk_qkv_rope at the same position) @ Wo^T
     assert not torch.equal(x1, x0)
+    from zonos_amd.kvlayout import unpack_k, unpack_v
+    q = torch.empty(R, H * hd, dtype=torch.bfloat16, device=DEV)
+    kc3, vt3 = kc.clone(), vt.clone()
+    call("zk_qkv_rope", ptr(part), 1, R, 1, H, Hk, hd, ptr(freqs), ctx - 1, None, ptr(q), ptr(kc3), ptr(vt3), smax,
+         None, 0, None, s)
+    torch.cuda.synchronize()
+    kk = unpack_k(kc1.cpu().view(R, Hk, -1), smax)[:, :, :ctx].float()
+    vv = unpack_v(vt1.cpu().view(R, Hk, -1), smax)[:, :, :ctx].float()
+    att = F.scaled_dot_product_attention(q.cpu().view(R, 1, H, hd).transpose(1, 2).float(), kk, vv, enable_gqa=True)
+    att = att.transpose(1, 2).reshape(R, H * hd).to(torch.bfloat16)
+    ref = x0.float().cpu() + att.float() @ Wo_.float().t()
+    assert (x1.float().cpu() - ref).abs().max() < 0.07, (x1.float().cpu() - ref).abs().max()
 
 
 @pytest.mark.parametrize("M,pos,smax", [(2, 0, 256), (2, 31, 256), (2, 32, 512), (1, 600, 1280), (2, 1029, 1280),
