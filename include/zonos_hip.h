@@ -39,17 +39,27 @@ typedef struct zk_sampling_params {
     float min_p;              /* 0 disables */
     float linear, conf, quad; /* unified sampler; linear<=0 disables */
     int32_t top_k;            /* 0 disables */
-    int32_t rp_window;        /* repetition_penalty_window */
+    int32_t rp_window;        /* repetition_penalty_window; see "window contract" below */
     float cfg_scale;          /* classifier-free guidance scale (model.py:112-114) */
     int32_t force_full_length;/* benchmark mode: cb0 EOS logit forced to -inf every step */
 } zk_sampling_params;
 
 /* Standalone sampler over fp32 logits [B][K][V] (already CFG-combined).
  * generated: int64 [B][K][gen_stride] token history (the reference passes
- *            delayed_codes[..., :offset]); the last rp_window of the first `gen_len`
- *            columns are penalised; NULL => no repetition penalty (prefill call).
+ *            delayed_codes[..., :offset]), 0 <= gen_len <= gen_stride; tokens >= V count as V-1
+ *            (sampling.py:143), tokens must be >= 0; NULL => no repetition penalty (prefill call).
  * rp:        float [B] per-row repetition penalty (model.py:342,356).
- * out:       int64 [B][K] sampled tokens. */
+ * out:       int64 [B][K] sampled tokens.
+ *
+ * Window contract (all three sampler entries). The reference penalises generated[..., -rp_window:]
+ * (sampling.py:142), so the penalised columns are the last W of the first gen_len, with
+ *     W = gen_len                  when rp_window == 0 (Python's -0: selects everything),
+ *     W = min(rp_window, gen_len)  otherwise;
+ * rp_window == 0 does not switch the penalty off (rp == 1 or generated == NULL does). The kernel holds
+ * at most 512 columns. zk_sample_logits and zk_sample_logits_torch know gen_len on the host: a call
+ * with W <= 512 matches the reference, a call with W > 512 returns an error and launches nothing.
+ * zk_sample_heads reads the history length from the device word scal[0], which outgrows 512 during a
+ * generation: it takes 1 <= rp_window <= 512 only and returns an error otherwise. */
 int zk_sample_logits(const float* logits, int B, int K, int V,
                      const int64_t* generated, int gen_stride, int gen_len, const float* rp,
                      const zk_sampling_params* sp, uint64_t seed, int step, int draw, int row_base,
@@ -58,7 +68,8 @@ int zk_sample_logits(const float* logits, int B, int K, int V,
 /* zk_sample_logits with torch's GPU noise instead of the keyed stream: the [B][K][V] race noise is
  * what `torch.empty_like(logits).exponential_(1)` returns when torch's CUDA generator holds
  * (seed, offset) (sampling.py:26-28); stride from zk_torch_noise_policy(B*K*V, ...). The caller
- * advances the generator by the policy's incr, as torch's own call would. */
+ * advances the generator by the policy's incr, as torch's own call would. History, window contract
+ * and refusals as zk_sample_logits. */
 int zk_sample_logits_torch(const float* logits, int B, int K, int V,
                            const int64_t* generated, int gen_stride, int gen_len, const float* rp,
                            const zk_sampling_params* sp, uint64_t seed, uint64_t offset, int stride,
@@ -299,7 +310,8 @@ typedef struct zk_gen_state {
  * (model.py:112-115), biased (model.py:322-324,353,360-362) and sampled. prefill=1 is the
  * first sample (model.py:304: no bias, no penalty). draw 1 = EOS resample (model.py:386-393):
  * a no-op unless some row has a new EOS. dbg_logits (nullable) receives the fp32 CFG logits
- * before bias [B][K][V]. */
+ * before bias [B][K][V]. The history is st->delayed[..., :scal[0]]; sp->rp_window must be in
+ * [1, 512] (the window contract at zk_sample_logits), anything else is an error return. */
 int zk_sample_heads(const float* part, int nsplit, const zk_gen_state* st, const zk_sampling_params* sp,
                     int prefill, int draw, float* dbg_logits, void* stream);
 /* EOS protocol + frame write + counters (model.py:376-424); prefill=1 only writes the

@@ -257,9 +257,12 @@ struct RowCtx {
 template <bool TN>
 ZK_DEV int sample_row(float* x, const RowCtx& c, const zk_sampling_params& sp, Smem& s) {
     const int V = c.V;
-    // ---- repetition penalty (sampling.py:142-169); rp == 1 is an exact identity
-    if (c.gen != nullptr && sp.rp_window > 0) {
-        const int W = min(min(sp.rp_window, c.gen_len), MAXW);
+    // ---- repetition penalty (sampling.py:142-169); rp == 1 is an exact identity. The reference slices
+    // generated[..., -window:]: a window of 0 is the whole history (Python's -0: selects everything),
+    // as is a window beyond it. The entries refuse what does not fit MAXW (effective_window; the heads
+    // entry by rp_window alone); the min() here only keeps the LDS window in bounds.
+    if (c.gen != nullptr) {
+        const int W = min(sp.rp_window > 0 ? min(sp.rp_window, c.gen_len) : c.gen_len, MAXW);
         const int j0 = c.gen_len - W;
         for (int j = threadIdx.x; j < W; j += NT) {
             const int64_t t = c.gen[j0 + j];
@@ -523,6 +526,10 @@ __global__ void k_delay_revert(const int64_t* d, int B, int K, int L, int64_t* o
     }
 }
 
+// The columns the reference's generated[..., -window:] selects from a history of gen_len
+// (sampling.py:142): all of them for window 0 and for a window beyond the history.
+int effective_window(int rp_window, int gen_len) { return rp_window == 0 ? gen_len : std::min(rp_window, gen_len); }
+
 }  // namespace
 
 extern "C" int zk_sample_logits(const float* logits, int B, int K, int V, const int64_t* generated,
@@ -532,6 +539,11 @@ extern "C" int zk_sample_logits(const float* logits, int B, int K, int V, const 
     ZK_REQUIRE(B > 0 && K > 0, "zk_sample_logits: empty batch");
     ZK_REQUIRE(sp != nullptr, "zk_sample_logits: null params");
     ZK_REQUIRE(sp->top_k >= 0 && sp->rp_window >= 0, "zk_sample_logits: negative top_k/window");
+    ZK_REQUIRE(generated == nullptr || (gen_len >= 0 && gen_stride >= gen_len),
+               "zk_sample_logits: gen_len=%d must be in [0, gen_stride=%d]", gen_len, gen_stride);
+    ZK_REQUIRE(generated == nullptr || effective_window(sp->rp_window, gen_len) <= MAXW,
+               "zk_sample_logits: repetition window %d over a history of %d columns penalises %d columns, more "
+               "than %d", sp->rp_window, gen_len, effective_window(sp->rp_window, gen_len), MAXW);
     hipLaunchKernelGGL(k_sample_logits<false>, dim3(B * K), dim3(NT), 0, (hipStream_t)stream, logits, B, K, V,
                        generated, gen_stride, gen_len, rp, *sp, seed, step, draw, row_base, (uint64_t)0, 0, out);
     ZK_CHECK_LAUNCH("zk_sample_logits");
@@ -546,6 +558,11 @@ extern "C" int zk_sample_logits_torch(const float* logits, int B, int K, int V, 
     ZK_REQUIRE(sp != nullptr, "zk_sample_logits_torch: null params");
     ZK_REQUIRE(sp->top_k >= 0 && sp->rp_window >= 0, "zk_sample_logits_torch: negative top_k/window");
     ZK_REQUIRE(stride > 0 && stride % 256 == 0, "zk_sample_logits_torch: stride %d (256 x grid)", stride);
+    ZK_REQUIRE(generated == nullptr || (gen_len >= 0 && gen_stride >= gen_len),
+               "zk_sample_logits_torch: gen_len=%d must be in [0, gen_stride=%d]", gen_len, gen_stride);
+    ZK_REQUIRE(generated == nullptr || effective_window(sp->rp_window, gen_len) <= MAXW,
+               "zk_sample_logits_torch: repetition window %d over a history of %d columns penalises %d columns, "
+               "more than %d", sp->rp_window, gen_len, effective_window(sp->rp_window, gen_len), MAXW);
     hipLaunchKernelGGL(k_sample_logits<true>, dim3(B * K), dim3(NT), 0, (hipStream_t)stream, logits, B, K, V,
                        generated, gen_stride, gen_len, rp, *sp, seed, 0, 0, 0, offset, stride, out);
     ZK_CHECK_LAUNCH("zk_sample_logits_torch");
@@ -584,6 +601,11 @@ extern "C" int zk_sample_heads(const float* part, int nsplit, const zk_gen_state
                                void* stream) {
     ZK_REQUIRE(st && sp && part, "zk_sample_heads: null argument");
     ZK_REQUIRE(st->V > 0 && st->V <= NT * NPT, "zk_sample_heads: V=%d unsupported", st->V);
+    // the history length is the device word scal[0] and outgrows MAXW during generation: only a window
+    // that fits whatever the history holds is taken (0 would be the whole history, sampling.py:142)
+    ZK_REQUIRE(sp->rp_window >= 1 && sp->rp_window <= MAXW,
+               "zk_sample_heads: repetition window %d must be in [1, %d] (0 penalises the whole history, which "
+               "outgrows the kernel's window)", sp->rp_window, MAXW);
     ZK_REQUIRE(!st->noise_mode || (st->noise_stride > 0 && st->noise_stride % 256 == 0 && st->noise_incr > 0),
                "zk_sample_heads: torch noise needs a stride (256 x grid) and an increment (zk_torch_noise_policy)");
     auto kern = st->noise_mode ? k_sample_heads<true> : k_sample_heads<false>;

@@ -34,6 +34,7 @@ from ._lib import GenState, SamplingParams, call, ptr
 
 EOS, MASK, UNKNOWN = 1024, 1025, -1
 KV_DTYPES = ("bf16", "fp8")
+RP_WINDOW_MAX = 512          # sampler.hip MAXW: the repetition-penalty window the sampler holds in LDS
 
 
 def resolve_kv_dtype(kv_dtype: str | None) -> str:
@@ -43,6 +44,18 @@ def resolve_kv_dtype(kv_dtype: str | None) -> str:
     if kv_dtype not in KV_DTYPES:
         raise ValueError(f"kv_dtype must be one of {KV_DTYPES}, not {kv_dtype!r}")
     return kv_dtype
+
+
+def check_sampling_params(spd: dict) -> None:
+    """generate()'s refusals of sampling parameters the sampler would not treat as the reference does. The
+    reference slices generated[..., -window:] (sampling.py:142): a window of 0 is the whole history, which
+    outgrows the sampler's window during generation (zk_sample_heads refuses the same values)."""
+    rpw = int(spd["repetition_penalty_window"])
+    if not 1 <= rpw <= RP_WINDOW_MAX:
+        raise ValueError(f"repetition_penalty_window={rpw} must be in [1, {RP_WINDOW_MAX}]: 0 penalises the "
+                         f"whole history in the reference (it does not switch the penalty off; "
+                         f"repetition_penalty=1.0 does) and the sampler holds {RP_WINDOW_MAX} columns")
+
 
 N_CB = 9
 VOCAB = 1026
@@ -544,6 +557,7 @@ class HipDecoder(HipBackbone):
         spd = dict(top_p=0, top_k=0, min_p=0, linear=0.55, conf=0.4, quad=0.0, repetition_penalty=3.0,
                    repetition_penalty_window=2, temperature=1.0)
         spd.update(sampling_params or {})
+        check_sampling_params(spd)
         c = self.cfg
         B = batch_size
         R = 2 * B

@@ -148,9 +148,9 @@ def log_sampling_stats(logits_row: torch.Tensor, sp: dict, generated_row: torch.
         print(f"Temperature: {sp['temperature']}, Top P: {sp['top_p']}, Top K: {sp['top_k']}, "
               f"Min P: {sp['min_p']}, Linear: {sp['linear']}, Conf: {sp['conf']}, Quad: {sp['quad']} | "
               f"RepPen: {sp['repetition_penalty']}, RepPenWindow: {sp['repetition_penalty_window']}")
-    W = int(sp.get("repetition_penalty_window", 0))
-    if rp != 1.0 and generated_row is not None and W > 0:
-        g = generated_row.detach().cpu()[-W:].clamp_max(V - 1).long()
+    W = int(sp.get("repetition_penalty_window", 2))          # the reference's default (sampling.py:243)
+    if rp != 1.0 and generated_row is not None:
+        g = generated_row.detach().cpu()[-W:].clamp_max(V - 1).long()      # (-0: is the whole history, as :142)
         f = torch.ones(V).scatter_reduce(0, g, torch.full((g.numel(),), float(rp)), reduce="prod")
         x = torch.where(x <= 0, x * f, x / f)
     temperature = float(sp["temperature"])
