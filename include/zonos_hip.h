@@ -168,6 +168,26 @@ int zk_permute_fc1(const void* w_fc1, int F, int D, void* w_out, void* stream);
  * out holds ceil64(N)*K elements. K % 64 == 0. */
 int zk_pack_weights(const void* w, int N, int K, void* out, void* stream);
 
+/* Opt-in FP8 (e4m3fn) weights of the small-batch GEMVs (generate(weight_dtype="fp8"); format and packed
+ * image: zonos_amd/wlayout.py). zk_pack_weights_e4m3 is the load-time quantiser, the FP8 counterpart of
+ * zk_pack_weights: nn.Linear weight [N][K] bf16 (fc1: in zk_permute_fc1 order) -> OCP e4m3fn bytes with one
+ * power-of-two scale per output row (biased exponent byte, 2^(b-127); the scale rule of
+ * zk_kv_quantize_e4m3 on the row's amax), out = the packed image [ceil64(N)/16][K/64][64][2][8] bytes
+ * (ceil64(N)*K bytes; rows >= N zero), scales = uint8 [ceil64(N)] (rows >= N: 127). K % 64 == 0.
+ * The three GEMV entries are their bf16 counterparts with the byte image and its scales in place of W:
+ * same argument checks, same layout / K split / summation order per shape, so each returns the bits of
+ * the bf16 entry on zk_pack_weights(dequantised weights). */
+int zk_pack_weights_e4m3(const void* w, int N, int K, void* out, void* scales, void* stream);
+int zk_gemv_fused_w8(const void* A, long lda, const void* W8, const void* w_scale, int M, int N, int K, int mode,
+                     const void* ln_w, const void* ln_b, float eps, float* Cf, void* Cb,
+                     const int32_t* skip, void* stream);
+int zk_gemv_qkv_rope_w8(const void* x, const void* W8, const void* w_scale, int M, int H, int Hkv, int hd,
+                        const void* ln_w, const void* ln_b, float eps, void* q_out, void* k_cache,
+                        void* vt_cache, int Smax, const int32_t* pos_dev, const float* freqs,
+                        const int32_t* skip, void* stream);
+int zk_gemv_attn_out_w8(const float* work, int nsplit, int Hkv, const void* W8, const void* w_scale, int M,
+                        int N, int K, void* x, const int32_t* skip, void* stream);
+
 /* Sum split-K slabs of in_proj, round to bf16, apply interleaved RoPE to q and k
  * (apply_rotary_emb _torch.py:18-30; positions pos0 + t (+ *pos_dev if non-NULL);
  * freqs = precompute_freqs_cis table [16384][hd/2][2], _torch.py:9-15), store q
@@ -331,7 +351,11 @@ int zk_eos_step(const zk_gen_state* st, int prefill, int prefix_len, void* strea
  * Replaces the per-token Python loop body of model.py:322-424 for a C/C++ host.
  * kv_fp8 = 1 (opt-in FP8 KV cache; a zeroed field is the bf16 cache): the seven-launch sequence at any
  * batch size with zk_attn_decode_qkv_f8 as the attention; together with small = 1, or with a layer whose
- * scale pointers (zk_prefill: or the scratch pair) are missing, both entries fail before any launch. */
+ * scale pointers (zk_prefill: or the scratch pair) are missing, both entries fail before any launch.
+ * w_fp8 = 1 (opt-in FP8 weights; a zeroed field is the bf16 weights): zk_decode_step runs the five-launch
+ * sequence with the _w8 GEMV entries on each layer's byte images (the heads stay bf16); it fails before any
+ * launch unless small = 1, kv_fp8 = 0 and every layer has its four images and scales. zk_prefill ignores
+ * the field and uses the bf16 weights. */
 typedef struct zk_step_layer {
     const void* ln1_w;    /* norm.weight / bias (bf16 [D]) */
     const void* ln1_b;
@@ -346,6 +370,16 @@ typedef struct zk_step_layer {
     void* vt_cache;
     void* k_scale;        /* kv_fp8 only: the scale bytes uint8 [2B][n_kv][smax] of K and of V */
     void* v_scale;
+    /* w_fp8 only: the packed e4m3fn images (zk_pack_weights_e4m3) of wqkv / wo / fc1 / fc2 and their
+     * scale bytes uint8 [ceil64(N)] */
+    const void* wqkv8;
+    const void* wo8;
+    const void* fc18;
+    const void* fc28;
+    const void* wqkv_scale;
+    const void* wo_scale;
+    const void* fc1_scale;
+    const void* fc2_scale;
 } zk_step_layer;
 
 typedef struct zk_step_desc {
@@ -376,6 +410,7 @@ typedef struct zk_step_desc {
     void* pre_k;
     void* pre_vt;
     int32_t pre_smax;
+    int32_t w_fp8;                 /* 0: bf16 weights; 1: FP8 (e4m3fn) layer weights, small must be 1 (above) */
 } zk_step_desc;
 
 int zk_decode_step(const zk_step_desc* d, void* stream);

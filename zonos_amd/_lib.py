@@ -38,7 +38,9 @@ class GenState(C.Structure):
 
 class StepLayer(C.Structure):
     _fields_ = [("ln1_w", P), ("ln1_b", P), ("wqkv", P), ("wo", P), ("ln2_w", P), ("ln2_b", P), ("fc1", P),
-                ("fc2", P), ("k_cache", P), ("vt_cache", P), ("k_scale", P), ("v_scale", P)]
+                ("fc2", P), ("k_cache", P), ("vt_cache", P), ("k_scale", P), ("v_scale", P),
+                ("wqkv8", P), ("wo8", P), ("fc18", P), ("fc28", P), ("wqkv_scale", P), ("wo_scale", P),
+                ("fc1_scale", P), ("fc2_scale", P)]
 
 
 class StepDesc(C.Structure):
@@ -48,7 +50,7 @@ class StepDesc(C.Structure):
               [("eps", F), ("kv_fp8", C.c_int32), ("layers", P), ("emb", P), ("heads", P), ("lnf_w", P), ("lnf_b", P),
                ("freqs", P), ("x", P), ("xn", P), ("y", P), ("h", P), ("part", P), ("attn_work", P), ("attn_cnt", P),
                ("dbg", P), ("st", GenState), ("sp", SamplingParams), ("pre_k", P), ("pre_vt", P),
-               ("pre_smax", C.c_int32)]
+               ("pre_smax", C.c_int32), ("w_fp8", C.c_int32)]
 
 
 class HybridLayer(C.Structure):
@@ -116,6 +118,10 @@ _SIGS = {
     "zk_gemv_fused": [P, L, P, I, I, I, I, P, P, F, P, P, P, P],
     "zk_permute_fc1": [P, I, I, P, P],
     "zk_pack_weights": [P, I, I, P, P],
+    "zk_pack_weights_e4m3": [P, I, I, P, P, P],
+    "zk_gemv_fused_w8": [P, L, P, P, I, I, I, I, P, P, F, P, P, P, P],
+    "zk_gemv_qkv_rope_w8": [P, P, P, I, I, I, I, P, P, F, P, P, P, I, P, P, P, P],
+    "zk_gemv_attn_out_w8": [P, I, I, P, P, I, I, I, P, P, P],
     "zk_qkv_rope": [P, I, I, I, I, I, I, P, I, P, P, P, P, I, P, I, P, P],
     "zk_attn_decode": [P, P, P, I, I, I, I, I, I, P, P, I, P, P, P],
     "zk_attn_decode_qkv": [P, I, P, P, P, I, I, I, I, I, I, P, P, I, P, I, P, P],

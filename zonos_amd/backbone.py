@@ -96,8 +96,12 @@ class HipZonosBackbone(nn.Module):
                                      prefix="")
         return self._core
 
-    def allocate_inference_cache(self, batch_size: int, max_seqlen: int, dtype=torch.bfloat16):
+    def allocate_inference_cache(self, batch_size: int, max_seqlen: int, dtype=torch.bfloat16, *,
+                                 weight_dtype: str = "bf16"):
         """_torch.py:64-71: one KV cache per layer, here in the engine layout (bf16 only)."""
+        if weight_dtype != "bf16":
+            raise ValueError("the backbone plugin runs the bf16 weights; the FP8 weights are "
+                             "generate(weight_dtype='fp8') of the engine")
         if dtype in ("fp8", torch.float8_e4m3fn):
             raise ValueError("the backbone plugin keeps a bf16 KV cache; the FP8 cache is generate(kv_dtype='fp8')")
         assert dtype == torch.bfloat16, "the HIP attention kernels read a bf16 cache"
@@ -249,9 +253,10 @@ class HipHybridBackbone(HipZonosBackbone):
                                         prefix="")
         return self._core
 
-    def allocate_inference_cache(self, batch_size: int, max_seqlen: int, dtype=torch.bfloat16):
-        if not self.hybrid:
-            return super().allocate_inference_cache(batch_size, max_seqlen, dtype)
+    def allocate_inference_cache(self, batch_size: int, max_seqlen: int, dtype=torch.bfloat16, *,
+                                 weight_dtype: str = "bf16"):
+        if weight_dtype != "bf16" or not self.hybrid:           # (the refusal of FP8 weights is the base class's)
+            return super().allocate_inference_cache(batch_size, max_seqlen, dtype, weight_dtype=weight_dtype)
         assert dtype == torch.bfloat16, "the HIP kernels keep bf16 caches and states"
         c = self.ecfg
         dev = self.norm_f.weight.device

@@ -15,6 +15,10 @@
 // links in a host-only build that provides just the entries it drives; fp8_ok() refuses kv_fp8 without them.
 #pragma weak zk_attn_decode_qkv_f8
 #pragma weak zk_kv_quantize_e4m3
+// The FP8-weight GEMV entries (gemm.hip), weak in the same way; w8_ok() refuses w_fp8 without them.
+#pragma weak zk_gemv_fused_w8
+#pragma weak zk_gemv_qkv_rope_w8
+#pragma weak zk_gemv_attn_out_w8
 
 static thread_local char g_err[1024] = "";
 
@@ -32,7 +36,7 @@ extern "C" int zk_version(void) { return 1; }
 // sizeof / offsetof of the by-value ABI structs, so a binding (ctypes here) can verify its
 // layout without a GPU: which = 0 zk_sampling_params, 1 zk_gen_state, 4 ZkCondSeg, 5 ZkCondPlan,
 // 6 zk_step_layer, 7 zk_step_desc, 8 zk_dac_desc; 12-25 sizes / field offsets (see the cases);
-// 26-30 zk_spk_block / zk_spk_desc.
+// 26-30 zk_spk_block / zk_spk_desc; 31-32 the FP8-weight fields of zk_step_desc / zk_step_layer.
 extern "C" long zk_abi_size(int which) {
     switch (which) {
         case 0: return (long)sizeof(zk_sampling_params);
@@ -61,6 +65,8 @@ extern "C" long zk_abi_size(int which) {
         case 28: return (long)offsetof(zk_spk_block, wd);
         case 29: return (long)offsetof(zk_spk_desc, blocks);
         case 30: return (long)offsetof(zk_spk_desc, lda_b);
+        case 31: return (long)offsetof(zk_step_desc, w_fp8);
+        case 32: return (long)offsetof(zk_step_layer, wqkv8);
         default: return -1;
     }
 }
@@ -286,6 +292,54 @@ int fp8_ok(const char* who, const zk_step_desc* d, bool prefill, int S) {
     }
     return 0;
 }
+
+// w_fp8 descriptors are checked whole before the first launch
+int w8_ok(const char* who, const zk_step_desc* d) {
+    if (!d->w_fp8) return 0;
+    if (&zk_gemv_fused_w8 == nullptr || &zk_gemv_qkv_rope_w8 == nullptr || &zk_gemv_attn_out_w8 == nullptr) {
+        zk_set_error("%s: this build has no FP8-weight GEMV kernels", who);
+        return -1;
+    }
+    if (!d->small || d->kv_fp8) {
+        zk_set_error("%s: w_fp8 = 1 runs the five-launch sequence on the bf16 KV cache only (small must be 1, "
+                     "kv_fp8 0)", who);
+        return -1;
+    }
+    for (int i = 0; i < d->n_layer; ++i) {
+        const zk_step_layer& L = d->layers[i];
+        if (L.wqkv8 == nullptr || L.wo8 == nullptr || L.fc18 == nullptr || L.fc28 == nullptr ||
+            L.wqkv_scale == nullptr || L.wo_scale == nullptr || L.fc1_scale == nullptr || L.fc2_scale == nullptr) {
+            zk_set_error("%s: w_fp8 layer %d lacks a weight image or its scale pointer", who, i);
+            return -1;
+        }
+    }
+    return 0;
+}
+
+// The small-batch layer GEMVs of one step, on the bf16 weights or (w_fp8) on the byte images: the same three
+// entries with the image and its scales in place of W
+struct StepGemv {
+    bool w8;
+    void* stream;
+    int fused(const void* A, long lda, const void* W, const void* W8, const void* sc, int M, int N, int K, int mode,
+              const void* ln_w, const void* ln_b, float eps, float* Cf, void* Cb, const int32_t* skip) const {
+        return w8 ? zk_gemv_fused_w8(A, lda, W8, sc, M, N, K, mode, ln_w, ln_b, eps, Cf, Cb, skip, stream)
+                  : zk_gemv_fused(A, lda, W, M, N, K, mode, ln_w, ln_b, eps, Cf, Cb, skip, stream);
+    }
+    int qkv_rope(const zk_step_desc* d, const zk_step_layer& L, int R, const int32_t* pos, const int32_t* skip) const {
+        const int H = d->n_heads, Hk = d->n_kv, hd = d->head_dim;
+        return w8 ? zk_gemv_qkv_rope_w8(d->x, L.wqkv8, L.wqkv_scale, R, H, Hk, hd, L.ln1_w, L.ln1_b, d->eps, d->y,
+                                        L.k_cache, L.vt_cache, d->smax, pos, d->freqs, skip, stream)
+                  : zk_gemv_qkv_rope(d->x, L.wqkv, R, H, Hk, hd, L.ln1_w, L.ln1_b, d->eps, d->y, L.k_cache, L.vt_cache,
+                                     d->smax, pos, d->freqs, skip, stream);
+    }
+    int attn_out(const zk_step_desc* d, const zk_step_layer& L, int R, const int32_t* skip) const {
+        const int D = d->d_model, Kd = d->n_heads * d->head_dim;
+        return w8 ? zk_gemv_attn_out_w8(d->attn_work, d->attn_merge, d->n_kv, L.wo8, L.wo_scale, R, D, Kd, d->x, skip,
+                                        stream)
+                  : zk_gemv_attn_out(d->attn_work, d->attn_merge, d->n_kv, L.wo, R, D, Kd, d->x, skip, stream);
+    }
+};
 }  // namespace
 
 extern "C" int zk_decode_step(const zk_step_desc* d, void* stream) {
@@ -294,6 +348,7 @@ extern "C" int zk_decode_step(const zk_step_desc* d, void* stream) {
         return -1;
     }
     ZK_STEP(fp8_ok("zk_decode_step", d, false, 0));
+    ZK_STEP(w8_ok("zk_decode_step", d));
     const int K = d->st.K, V = d->st.V, B = d->B, R = 2 * B;
     const int D = d->d_model, H = d->n_heads, Hk = d->n_kv, hd = d->head_dim, Fd = d->d_ff;
     const int Nqkv = (H + 2 * Hk) * hd;
@@ -312,33 +367,35 @@ extern "C" int zk_decode_step(const zk_step_desc* d, void* stream) {
         return decode_tail(d, d->split_heads, stream);
     }
     // B <= 8: five launches per block, the attention (through out_proj) in one of three forms
+    const StepGemv gv{d->w_fp8 != 0, stream};
     for (int i = 0; i < d->n_layer; ++i) {
         const zk_step_layer& L = d->layers[i];
         if (d->attn_merge > 0 && !d->rope_neox) {
             // B = 1: RoPE + KV write in the in_proj epilogue, a prologue-free attention over 32-key
             // slices, its partials merged by the out_proj GEMV
-            ZK_STEP(zk_gemv_qkv_rope(d->x, L.wqkv, R, H, Hk, hd, L.ln1_w, L.ln1_b, d->eps, d->y, L.k_cache,
-                                     L.vt_cache, d->smax, pos, d->freqs, skip, stream));
+            ZK_STEP(gv.qkv_rope(d, L, R, pos, skip));
             ZK_STEP(zk_attn_decode_q_part(d->y, L.k_cache, L.vt_cache, R, H, Hk, hd, d->smax, 1, pos, d->attn_work,
                                           d->attn_merge, skip, stream));
-            ZK_STEP(zk_gemv_attn_out(d->attn_work, d->attn_merge, Hk, L.wo, R, D, H * hd, d->x, skip, stream));
+            ZK_STEP(gv.attn_out(d, L, R, skip));
         } else {
-            ZK_STEP(zk_gemv_fused(d->x, D, L.wqkv, R, Nqkv, D, 0, L.ln1_w, L.ln1_b, d->eps, d->part, nullptr, skip,
-                                  stream));
+            ZK_STEP(gv.fused(d->x, D, L.wqkv, L.wqkv8, L.wqkv_scale, R, Nqkv, D, 0, L.ln1_w, L.ln1_b, d->eps, d->part,
+                             nullptr, skip));
             if (d->attn_merge > 0) {
                 ZK_STEP(zk_attn_decode_qkv_part(d->part, 1, d->freqs, L.k_cache, L.vt_cache, R, H, Hk, hd, d->smax, 1,
                                                 pos, d->attn_work, d->attn_merge, d->rope_neox, skip, stream));
-                ZK_STEP(zk_gemv_attn_out(d->attn_work, d->attn_merge, Hk, L.wo, R, D, H * hd, d->x, skip, stream));
+                ZK_STEP(gv.attn_out(d, L, R, skip));
             } else {
                 ZK_STEP(zk_attn_decode_qkv_sc(d->part, 1, d->freqs, L.k_cache, L.vt_cache, R, H, Hk, hd, d->smax, 1,
                                               pos, d->attn_work, d->attn_splits, d->attn_cnt, d->y, d->rope_neox,
                                               skip, stream));
-                ZK_STEP(zk_gemv_fused(d->y, H * hd, L.wo, R, D, H * hd, 2, nullptr, nullptr, d->eps, nullptr, d->x,
-                                      skip, stream));
+                ZK_STEP(gv.fused(d->y, H * hd, L.wo, L.wo8, L.wo_scale, R, D, H * hd, 2, nullptr, nullptr, d->eps,
+                                 nullptr, d->x, skip));
             }
         }
-        ZK_STEP(zk_gemv_fused(d->x, D, L.fc1, R, 2 * Fd, D, 1, L.ln2_w, L.ln2_b, d->eps, nullptr, d->h, skip, stream));
-        ZK_STEP(zk_gemv_fused(d->h, Fd, L.fc2, R, D, Fd, 2, nullptr, nullptr, d->eps, nullptr, d->x, skip, stream));
+        ZK_STEP(gv.fused(d->x, D, L.fc1, L.fc18, L.fc1_scale, R, 2 * Fd, D, 1, L.ln2_w, L.ln2_b, d->eps, nullptr, d->h,
+                         skip));
+        ZK_STEP(gv.fused(d->h, Fd, L.fc2, L.fc28, L.fc2_scale, R, D, Fd, 2, nullptr, nullptr, d->eps, nullptr, d->x,
+                         skip));
     }
     // 9 heads (model.py:104-111) with norm_f as the GEMV prologue, one slab
     ZK_STEP(zk_gemv_fused(d->x, D, d->heads, R, K * V, D, 0, d->lnf_w, d->lnf_b, d->eps, d->part, nullptr, skip,

@@ -99,7 +99,7 @@ def generate_sharded(model, prefix_conditioning: torch.Tensor, audio_prefix_code
                      max_new_tokens: int = 86 * 30, cfg_scale: float = 2.0, batch_size: int = 1,
                      sampling_params: dict | None = None, *, seed: int | None = None, group=None,
                      gather: bool = True, local_input: bool = False, coll_device=None, return_local: bool = False,
-                     uniform_shards: bool = True, **generate_kw):
+                     uniform_shards: bool = True, weight_dtype: str | None = None, **generate_kw):
     """Zonos.generate (model.py:224-457) of a GLOBAL batch of ``batch_size`` utterances sharded over
     the ranks of ``group`` (one process per GPU) -- the library form of zonos_batch_cli.py:113-162's
     batching with the batch split across the node's GPUs.
@@ -121,7 +121,10 @@ def generate_sharded(model, prefix_conditioning: torch.Tensor, audio_prefix_code
       ``return_local`` returns (the rank's own list on its device, the gathered list).
     ``model`` is a ``zonos_amd.model.Zonos`` or an engine (``HipDecoder`` / ``HybridDecoder``);
     extra keywords (``kv_dtype="fp8"`` among them) go to its ``generate``. Without an initialised process group this is
-    ``model.generate`` on the whole batch."""
+    ``model.generate`` on the whole batch.
+    ``weight_dtype`` ("bf16" / "fp8", None: the environment variable ZONOS_WEIGHT_DTYPE) goes to ``generate`` too:
+    the opt-in FP8 layer weights of the small-batch path, so every rank's share must be at most 8 utterances."""
+    generate_kw = dict(generate_kw, weight_dtype=weight_dtype)
     world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
     rank = dist.get_rank(group) if world > 1 else 0
     row_base, local, run = padded_shard(batch_size, world, rank)

@@ -15,7 +15,10 @@ Design (MI355X-first):
     SwiGLU epilogue, GEMM weights fragment-packed (zk_pack_weights). The KV cache stores
     per (row, kv head) 32-key slices in MFMA-fragment order (zonos_amd.kvlayout), in bf16 or,
     opt-in (generate(kv_dtype="fp8") / ZONOS_KV_DTYPE=fp8), as e4m3fn bytes with one power-of-two
-    scale per key: half the KV memory and half the bytes the decode attention streams.
+    scale per key: half the KV memory and half the bytes the decode attention streams. Likewise opt-in
+    (generate(weight_dtype="fp8") / ZONOS_WEIGHT_DTYPE=fp8): the four linear weights of every block as
+    e4m3fn bytes with one power-of-two scale per output row (zonos_amd.wlayout), streamed by the B <= 8
+    step's GEMVs in place of the bf16 images, which stay for the prefill.
   * torch is plumbing only: it allocates device memory and provides the stream.
 """
 from __future__ import annotations
@@ -34,6 +37,7 @@ from ._lib import GenState, SamplingParams, call, ptr
 
 EOS, MASK, UNKNOWN = 1024, 1025, -1
 KV_DTYPES = ("bf16", "fp8")
+WEIGHT_DTYPES = ("bf16", "fp8")
 RP_WINDOW_MAX = 512          # sampler.hip MAXW: the repetition-penalty window the sampler holds in LDS
 
 
@@ -44,6 +48,15 @@ def resolve_kv_dtype(kv_dtype: str | None) -> str:
     if kv_dtype not in KV_DTYPES:
         raise ValueError(f"kv_dtype must be one of {KV_DTYPES}, not {kv_dtype!r}")
     return kv_dtype
+
+
+def resolve_weight_dtype(weight_dtype: str | None) -> str:
+    """generate()'s ``weight_dtype``: None reads the environment variable ZONOS_WEIGHT_DTYPE (default bf16)."""
+    if weight_dtype is None:
+        weight_dtype = os.environ.get("ZONOS_WEIGHT_DTYPE") or "bf16"
+    if weight_dtype not in WEIGHT_DTYPES:
+        raise ValueError(f"weight_dtype must be one of {WEIGHT_DTYPES}, not {weight_dtype!r}")
+    return weight_dtype
 
 
 def check_sampling_params(spd: dict) -> None:
@@ -96,6 +109,24 @@ def pack_weights(w: torch.Tensor, stream) -> torch.Tensor:
     out = torch.empty((N + 63) // 64 * 64, K, dtype=w.dtype, device=w.device)
     call("zk_pack_weights", ptr(w), N, K, ptr(out), stream)
     return out
+
+
+def unpack_weights(wp: torch.Tensor, N: int) -> torch.Tensor:
+    """Inverse of pack_weights: the fragment-packed image [ceil64(N)][K] -> nn.Linear order bf16 [N][K]."""
+    Np, K = wp.shape
+    x = wp.reshape(Np // 16, K // 32, 4, 16, 8)               # tile kc lg ln e  (lane = 16 lg + ln)
+    return x.permute(0, 3, 1, 2, 4).reshape(Np, K)[:N].contiguous()
+
+
+def pack_weights_e4m3(w: torch.Tensor, stream) -> tuple[torch.Tensor, torch.Tensor]:
+    """nn.Linear bf16 [N][K] -> (packed e4m3fn image uint8 [ceil64(N) * K], scale bytes uint8 [ceil64(N)]):
+    zk_pack_weights_e4m3, bit-identical to wlayout.pack_w8(*wlayout.quantize_w_e4m3(w))."""
+    N, K = w.shape
+    Np = (N + 63) // 64 * 64
+    out = torch.empty(Np * K, dtype=torch.uint8, device=w.device)
+    sc = torch.empty(Np, dtype=torch.uint8, device=w.device)
+    call("zk_pack_weights_e4m3", ptr(w), N, K, ptr(out), ptr(sc), stream)
+    return out, sc
 
 
 def _split_for(N: int, K: int, M: int, target_blocks: int = 256) -> int:
@@ -233,6 +264,22 @@ class HipBackbone:
     def splits(self, R: int) -> dict:
         return decode_splits(self.cfg, R)
 
+    W8_NAMES = ("wqkv", "wo", "fc1", "fc2")
+
+    def quantize_weights_fp8(self):
+        """The FP8 images of the four linear weights of every layer (L[name + "8"], L[name + "_scale"]), made
+        once from the bf16 images and kept beside them (+ 50 % of the layer weight memory): fc1 in its
+        zk_permute_fc1 order, as the bf16 image holds it."""
+        if self.layers and "wqkv8" in self.layers[0]:
+            return
+        c = self.cfg
+        rows = dict(wqkv=(c.n_heads + 2 * c.n_kv) * c.head_dim, wo=c.d_model, fc1=2 * c.d_ff, fc2=c.d_model)
+        stream = _lib.stream_ptr(self.device)
+        for L in self.layers:
+            for name in self.W8_NAMES:
+                L[name + "8"], L[name + "_scale"] = pack_weights_e4m3(unpack_weights(L[name], rows[name]), stream)
+        torch.cuda.synchronize(self.device)
+
     def _layers_small(self, ws, R: int, stream, skip):
         """Decode step of the 26 blocks for R <= 16 rows (B <= 8), five launches per block:
         [norm -> in_proj] -> attention (RoPE, KV write) -> [out_proj -> x += .] ->
@@ -243,34 +290,39 @@ class HipBackbone:
         Nqkv = (H + 2 * Hk) * hd
         x, y, h, part, scal = ws["x"], ws["y"], ws["h"], ws["part"], ws["scal"]
         merge = ws.get("attn_merge", 0)
+        w8 = bool(ws.get("w_fp8"))           # the _w8 entries on the byte images (same sequence, same arithmetic)
+
+        def W(L, name):                      # the weight argument(s) of a GEMV entry
+            return (ptr(L[name + "8"]), ptr(L[name + "_scale"])) if w8 else (ptr(L[name]),)
+
+        fused, qkv_rope, attn_out = (n + "_w8" if w8 else n for n in ("zk_gemv_fused", "zk_gemv_qkv_rope",
+                                                                       "zk_gemv_attn_out"))
         for i, L in enumerate(self.layers):
             kc, vt = self._kv(ws, i)
             if merge and not self.rope_neox:
                 # B = 1: RoPE + KV write in the in_proj epilogue (q -> y), prologue-free attention over
                 # 32-key slices, partials merged by the out_proj GEMV
-                call("zk_gemv_qkv_rope", ptr(x), ptr(L["wqkv"]), R, H, Hk, hd, ptr(L["ln1_w"]), ptr(L["ln1_b"]),
+                call(qkv_rope, ptr(x), *W(L, "wqkv"), R, H, Hk, hd, ptr(L["ln1_w"]), ptr(L["ln1_b"]),
                      c.eps, ptr(y), ptr(kc), ptr(vt), ws["smax"], ptr(scal[1:2]), ptr(self.freqs), skip, stream)
                 call("zk_attn_decode_q_part", ptr(y), ptr(kc), ptr(vt), R, H, Hk, hd, ws["smax"], 1, ptr(scal[1:2]),
                      ptr(ws["attn_work"]), merge, skip, stream)
-                call("zk_gemv_attn_out", ptr(ws["attn_work"]), merge, Hk, ptr(L["wo"]), R, D, H * hd, ptr(x), skip,
-                     stream)
+                call(attn_out, ptr(ws["attn_work"]), merge, Hk, *W(L, "wo"), R, D, H * hd, ptr(x), skip, stream)
             else:
-                call("zk_gemv_fused", ptr(x), D, ptr(L["wqkv"]), R, Nqkv, D, 0, ptr(L["ln1_w"]), ptr(L["ln1_b"]),
+                call(fused, ptr(x), D, *W(L, "wqkv"), R, Nqkv, D, 0, ptr(L["ln1_w"]), ptr(L["ln1_b"]),
                      c.eps, ptr(part), None, skip, stream)
                 if merge:
                     call("zk_attn_decode_qkv_part", ptr(part), 1, ptr(self.freqs), ptr(kc), ptr(vt), R, H, Hk, hd,
                          ws["smax"], 1, ptr(scal[1:2]), ptr(ws["attn_work"]), merge, self.rope_neox, skip, stream)
-                    call("zk_gemv_attn_out", ptr(ws["attn_work"]), merge, Hk, ptr(L["wo"]), R, D, H * hd, ptr(x),
-                         skip, stream)
+                    call(attn_out, ptr(ws["attn_work"]), merge, Hk, *W(L, "wo"), R, D, H * hd, ptr(x), skip, stream)
                 else:
                     call("zk_attn_decode_qkv_sc", ptr(part), 1, ptr(self.freqs), ptr(kc), ptr(vt), R, H, Hk, hd,
                          ws["smax"], 1, ptr(scal[1:2]), ptr(ws["attn_work"]), ws["attn_splits"],
                          ptr(ws["attn_cnt"]), ptr(y), self.rope_neox, skip, stream)
-                    call("zk_gemv_fused", ptr(y), H * hd, ptr(L["wo"]), R, D, H * hd, 2, None, None, c.eps, None,
+                    call(fused, ptr(y), H * hd, *W(L, "wo"), R, D, H * hd, 2, None, None, c.eps, None,
                          ptr(x), skip, stream)
-            call("zk_gemv_fused", ptr(x), D, ptr(L["fc1"]), R, 2 * Fd, D, 1, ptr(L["ln2_w"]), ptr(L["ln2_b"]),
+            call(fused, ptr(x), D, *W(L, "fc1"), R, 2 * Fd, D, 1, ptr(L["ln2_w"]), ptr(L["ln2_b"]),
                  c.eps, None, ptr(h), skip, stream)
-            call("zk_gemv_fused", ptr(h), Fd, ptr(L["fc2"]), R, D, Fd, 2, None, None, c.eps, None, ptr(x), skip,
+            call(fused, ptr(h), Fd, *W(L, "fc2"), R, D, Fd, 2, None, None, c.eps, None, ptr(x), skip,
                  stream)
 
     def _kv(self, ws, layer):
@@ -352,6 +404,8 @@ class HipDecoder(HipBackbone):
     embed_norm = True
     kv_fp8_supported = True         # generate(kv_dtype="fp8"): the transformer backbone only
     _fp8 = False                    # the running generate() uses the FP8 KV cache
+    w_fp8_supported = True          # generate(weight_dtype="fp8"): the transformer backbone's small-batch path only
+    _w8 = False                     # the running generate() uses the FP8 layer weights
 
     def __init__(self, cfg: EngineConfig, weights: dict, device="cuda"):
         super().__init__(cfg, weights, device)
@@ -395,7 +449,7 @@ class HipDecoder(HipBackbone):
         seq_len = Lc + T + N_CB
         smax = -(-seq_len // ATTN_CHUNK) * ATTN_CHUNK
         S_pre = Lc + P + 1
-        key = (B, Lc, P, max_new, "fp8" if self._fp8 else "bf16")
+        key = (B, Lc, P, max_new, "fp8" if self._fp8 else "bf16", "w8" if self._w8 else "w16")
         if self._ws is not None and self._ws["key"] == key:
             ws = self._ws
             for k in ws["state_keys"]:
@@ -410,6 +464,8 @@ class HipDecoder(HipBackbone):
                   attn_merge=attn_merge, state_keys=tuple(state), graph=None, **state,
                   **activation_buffers(self.cfg, self.device, R * S_pre, R, smax, splits, max(attn_splits, attn_merge)),
                   **generation_state(self.device, B, Ld))
+        if self._w8:
+            ws["w_fp8"] = True
         if self._fp8:
             # the bf16 K / V^T pair the exact prefill of one layer runs on (zeroed once: the prefill attention
             # multiplies the masked tail of its last 32-key slice by p = 0)
@@ -456,9 +512,11 @@ class HipDecoder(HipBackbone):
             arr = (_lib.StepLayer * c.n_layer)()
             for i, L in enumerate(self.layers):
                 kc, vt, ksc, vsc = self._kv8(ws, i) if ws.get("kv_fp8") else (*self._kv(ws, i), None, None)
+                # the FP8 images and scales: NULL before the first FP8 generate() has made them
+                w8 = [ptr(L.get(n + sfx)) for sfx in ("8", "_scale") for n in self.W8_NAMES]
                 arr[i] = _lib.StepLayer(ptr(L["ln1_w"]), ptr(L["ln1_b"]), ptr(L["wqkv"]), ptr(L["wo"]),
                                         ptr(L["ln2_w"]), ptr(L["ln2_b"]), ptr(L["fc1"]), ptr(L["fc2"]), ptr(kc), ptr(vt),
-                                        ptr(ksc), ptr(vsc))
+                                        ptr(ksc), ptr(vsc), *w8)
             ws["step_layers"] = arr
         sps = ws["splits"]
         return _lib.StepDesc(B, c.n_layer, c.d_model, c.n_heads, c.n_kv, c.head_dim, c.d_ff, ws["smax"],
@@ -468,7 +526,8 @@ class HipDecoder(HipBackbone):
                              ptr(self.lnf_b), ptr(self.freqs), ptr(ws["x"]), ptr(ws["xn"]), ptr(ws["y"]), ptr(ws["h"]),
                              ptr(ws["part"]), ptr(ws["attn_work"]), ptr(ws["attn_cnt"]), ptr(ws["dbg"]), st, sp,
                              ptr(ws["pre_kv"][0]) if "pre_kv" in ws else None,
-                             ptr(ws["pre_kv"][1]) if "pre_kv" in ws else None, ws.get("pre_smax", 0))
+                             ptr(ws["pre_kv"][1]) if "pre_kv" in ws else None, ws.get("pre_smax", 0),
+                             int(bool(ws.get("w_fp8"))))
 
     def _c_decode(self, ws, B, st, sp, stream):
         call("zk_decode_step", C.byref(self._step_desc(ws, B, st, sp)), stream)
@@ -516,8 +575,15 @@ class HipDecoder(HipBackbone):
                  seed: int = 0, row_base: int = 0, force_full_length: bool = False, callback=None,
                  progress=None, poll_every: int = 16, trace: dict | None = None, use_graph: bool = True,
                  _after_prefill=None, noise: str = "keyed", generator: torch.Generator | None = None,
-                 pad_rows: int = 0, kv_dtype: str | None = None):
+                 pad_rows: int = 0, kv_dtype: str | None = None, *, weight_dtype: str | None = None):
         """Zonos.generate (model.py:224-457). Returns the list of int64 [9, T_i] code tensors.
+
+        ``weight_dtype``: "bf16" (default) or "fp8" -- the four linear weights of every block as e4m3fn bytes
+        with one power-of-two scale per output row (zonos_amd.wlayout), streamed by the GEMVs of the B <= 8
+        decode step: half the weight bytes per step. The first such call quantises the weights once and keeps
+        the images beside the bf16 ones (the prefill, the heads and the embeddings stay bf16). None reads the
+        environment variable ZONOS_WEIGHT_DTYPE. ValueError where the small-batch path does not run: B > 8,
+        d_model != 2048, together with kv_dtype="fp8", the hybrid engine.
 
         ``kv_dtype``: "bf16" (default) or "fp8" -- the KV cache as e4m3fn bytes with one power-of-two scale
         per (row, kv head, key) (zonos_amd.kvlayout): half the KV memory and half the bytes the decode
@@ -548,7 +614,19 @@ class HipDecoder(HipBackbone):
         if kv_dtype == "fp8" and not (self.kv_fp8_supported and self.cfg.head_dim == 128 and not self.rope_neox):
             raise ValueError(f"kv_dtype='fp8' needs the transformer backbone with head_dim 128 "
                              f"({type(self).__name__}, head_dim {self.cfg.head_dim})")
+        weight_dtype = resolve_weight_dtype(weight_dtype)
+        if weight_dtype == "fp8":
+            if not (self.w_fp8_supported and self.small_batch_path):
+                raise ValueError(f"weight_dtype='fp8' needs the transformer backbone's small-batch decode path "
+                                 f"({type(self).__name__})")
+            if batch_size > 8 or self.cfg.d_model != 2048:
+                raise ValueError(f"weight_dtype='fp8' runs on the small-batch decode path only: batch_size <= 8 and "
+                                 f"d_model 2048 (batch_size {batch_size}, d_model {self.cfg.d_model})")
+            if kv_dtype == "fp8":
+                raise ValueError("weight_dtype='fp8' cannot be combined with kv_dtype='fp8' (the FP8 KV cache runs "
+                                 "the seven-launch sequence)")
         self._fp8 = kv_dtype == "fp8"
+        self._w8 = weight_dtype == "fp8"
         _lib.require_gpu(prefix_conditioning, "prefix_conditioning")
         if prefix_conditioning.dim() != 3 or prefix_conditioning.shape[2] != self.cfg.d_model:
             # zk_prefill copies rows of Lc * d_model bf16: a wrong width would read out of bounds
@@ -563,6 +641,8 @@ class HipDecoder(HipBackbone):
         R = 2 * B
         P = 0 if audio_prefix_codes is None else int(audio_prefix_codes.shape[2])
         Lc = int(prefix_conditioning.shape[1])
+        if self._w8:
+            self.quantize_weights_fp8()
         ws = self._alloc(B, Lc, P, max_new_tokens)
         stream = _lib.stream_ptr(self.device)
         T, Ld, S = ws["T"], ws["Ld"], ws["S_pre"]

@@ -121,7 +121,7 @@ class Zonos:
                  progress_bar: bool = True, disable_torch_compile: bool = False,
                  callback: Callable[[torch.Tensor, int, int], bool] | None = None, *, seed: int | None = None,
                  row_base: int = 0, force_full_length: bool = False, pad_rows: int = 0,
-                 kv_dtype: str | None = None):
+                 kv_dtype: str | None = None, weight_dtype: str | None = None):
         """model.py:224-457. ``disable_torch_compile`` is accepted and ignored (the step is a
         captured hipGraph). Sampling noise: by default (``seed`` None) the reference's own -- every
         sampler call takes the values `torch.empty_like(probs).exponential_(1)` would draw from torch's
@@ -135,7 +135,9 @@ class Zonos:
         accepted any ``row_base``; ``generate_sharded`` always passes a seed and is unaffected.)
         ``pad_rows``: trailing padding utterances kept out of the EOS protocol (HipDecoder.generate).
         ``kv_dtype``: "bf16" or "fp8" (the opt-in FP8 KV cache, HipDecoder.generate); None reads the
-        environment variable ZONOS_KV_DTYPE (default bf16), so unchanged callers can opt in."""
+        environment variable ZONOS_KV_DTYPE (default bf16), so unchanged callers can opt in.
+        ``weight_dtype``: "bf16" or "fp8" (the opt-in FP8 layer weights of the B <= 8 decode path,
+        HipDecoder.generate); None reads the environment variable ZONOS_WEIGHT_DTYPE (default bf16)."""
         noise = "torch" if seed is None else "keyed"
         if noise == "torch" and row_base:
             raise ValueError("row_base needs an explicit seed (the keyed noise stream)")
@@ -151,7 +153,8 @@ class Zonos:
         out = self.engine.generate(prefix_conditioning.to(self.device), audio_prefix_codes, max_new_tokens,
                                    cfg_scale, batch_size, sampling_params, seed=seed or 0, row_base=row_base,
                                    force_full_length=force_full_length, callback=callback, progress=prog,
-                                   noise=noise, pad_rows=pad_rows, kv_dtype=kv_dtype)
+                                   noise=noise, pad_rows=pad_rows, kv_dtype=kv_dtype,
+                                   weight_dtype=weight_dtype)
         if prog is not None:
             prog.close()
         return out
