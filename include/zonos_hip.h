@@ -635,6 +635,39 @@ size_t zk_dac_decode_workspace(const zk_dac_desc* d, int B, int T);
 int zk_dac_decode(const zk_dac_desc* d, const int64_t* codes, int B, int T, const int32_t* lens, void* workspace,
                   size_t workspace_bytes, float* out, void* stream);
 
+/* ---- Streaming: audio chunks of a generation that is still running (stream.hip). The reference decodes after
+ * generate() has returned (model.py:437-457, then autoencoder.py:44-47); these entries do the same work on a
+ * window of final frames. codes[b][k][t] = delayed[b][k][t + k + 1], so frame t is whole once column t + K is
+ * written: at a poll that read off = scal[0] - 1 the host passes upto = off - K BY VALUE (the device word moves
+ * on while the kernels run) and frames < upto are final. Windows are [f0, f1) in absolute code frames. */
+/* Window assembly: revert_delay_pattern (codebook_pattern.py), the `>= 1024 -> 0` fill and the per-row slice of
+ * model.py:437-451 on a window. delayed int64 [B][K][Ld]; P = audio-prefix frames; P <= f0 < f1; 0 <= upto <= Ld - K.
+ * end int32 [B]: the row's end frame if a first EOS (1024) of codebook 0 lies at a frame in [1, upto) -- model.py:439-440,
+ * argmax then `eos_pos == 0 -> length`, so an EOS at frame 0 counts as none and hides later ones -- else -1 (the row is
+ * live; its end is taken as upto). codes_w int64
+ * [B][K][f1 - f0]: un-delayed codes, ids >= 1024 and frames at or past the row's end as 0. lens_w int32 [B] =
+ * clamp(end_b - f0, 0, f1 - f0). Reads only columns < upto + K. */
+int zk_stream_window(const int64_t* delayed, int B, int K, int Ld, int P, int f0, int f1, int upto, int64_t* codes_w,
+                     int32_t* lens_w, int32_t* end, void* stream);
+/* The chunk [c0, c1) out of the window's waveform wav_w fp32 [B][1][(f1 - f0) hop] (f0 <= c0 < c1 <= f1): samples
+ * [(c0 - f0) hop, (min(end_b, c1) - f0) hop) of each row into chunk fp32 [B][(c1 - c0) hop], zero behind them; their
+ * count into n int32 [B] (0 for a row that ended before c0). end as zk_stream_window wrote it (-1: the row reaches c1). */
+int zk_stream_crop(const float* wav_w, int B, int hop, int f0, int c0, int c1, int f1, const int32_t* end, float* chunk,
+                   int32_t* n, void* stream);
+/* zk_stream_window -> the zk_dac_decode sequence on (codes_w, lens_w) -> zk_stream_crop, for the default fp16 pipeline.
+ * Refused before any launch, with zk_last_error starting "zk_stream_chunk:": a NULL pointer, f0 < P, a window not ordered
+ * f0 <= c0 < c1 <= f1, f1 > upto (only the device knows which rows have ended, so the host clamps f1 = min(c1 + H, upto)
+ * for every window; the kernel clamps through the row's end as well), upto > Ld - K, a workspace smaller than
+ * zk_stream_workspace(d, f1 - f0). workspace: device memory (window codes, lens, window waveform, the DAC workspace). */
+typedef struct zk_stream_desc {
+    const zk_dac_desc* dac;
+    const int64_t* delayed;    /* [B][K][Ld], the running generation's delayed codes (zk_gen_state.delayed) */
+    int32_t B, K, Ld, P;
+} zk_stream_desc;
+size_t zk_stream_workspace(const zk_stream_desc* d, int Wmax);    /* bytes for windows of <= Wmax frames; 0 if invalid */
+int zk_stream_chunk(const zk_stream_desc* d, int f0, int c0, int c1, int f1, int upto, void* workspace,
+                    size_t workspace_bytes, float* chunk_out, int32_t* n_out, int32_t* end_out, void* stream);
+
 /* ---- DAC encoder (prefix audio -> codes; DACAutoencoder.encode, autoencoder.py:27-28 ->
  * DacModel.encode). Convolutions run on zk_dac_conv_cl (channels-last fp16 operands); a strided
  * Conv1d(k = 2s, stride s, pad ceil(s/2)) runs as a stride-1 3-tap conv over the input folded to

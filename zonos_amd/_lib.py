@@ -88,6 +88,11 @@ class DacDesc(C.Structure):
                ("blocks", DacBlock * DAC_MAXB)]
 
 
+class StreamDesc(C.Structure):
+    _fields_ = [("dac", C.POINTER(DacDesc)), ("delayed", P), ("B", C.c_int32), ("K", C.c_int32), ("Ld", C.c_int32),
+                ("P", C.c_int32)]
+
+
 class SpkBlock(C.Structure):
     _fields_ = [("cin", C.c_int32), ("cout", C.c_int32), ("stride", C.c_int32), ("pad_", C.c_int32),
                 ("w1", P), ("scale1", P), ("shift1", P), ("w2", P), ("scale2", P), ("shift2", P),
@@ -138,6 +143,9 @@ _SIGS = {
     "zk_hybrid_decode_step": [C.POINTER(HybridDesc), P],
     "zk_hybrid_prefill": [C.POINTER(HybridDesc), P, I, I, P, P],
     "zk_dac_decode": [C.POINTER(DacDesc), P, I, I, P, P, C.c_size_t, P, P],
+    "zk_stream_window": [P, I, I, I, I, I, I, I, P, P, P, P],
+    "zk_stream_crop": [P, I, I, I, I, I, I, P, P, P, P],
+    "zk_stream_chunk": [C.POINTER(StreamDesc), I, I, I, I, I, P, C.c_size_t, P, P, P, P],
     "zk_mamba_step": [P, I, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, P],
     "zk_mamba_step_per_head": [P, I, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, P],
     "zk_mamba_prefill": [P, I, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P],
@@ -207,6 +215,8 @@ def load():
     lib.zk_abi_size.argtypes = [I]
     lib.zk_dac_decode_workspace.restype = C.c_size_t
     lib.zk_dac_decode_workspace.argtypes = [C.POINTER(DacDesc), I, I]
+    lib.zk_stream_workspace.restype = C.c_size_t
+    lib.zk_stream_workspace.argtypes = [C.POINTER(StreamDesc), I]
     lib.zk_dac_resunit_supported.restype = C.c_int
     lib.zk_dac_resunit_supported.argtypes = [I]
     lib.zk_gemm_warm_tiles.restype = C.c_int
@@ -223,7 +233,7 @@ def load():
 
 def exported_symbols() -> list[str]:
     return list(_SIGS) + ["zk_last_error", "zk_loudness_max_blocks", "zk_abi_size",
-                          "zk_dac_decode_workspace", "zk_dac_resunit_supported", "zk_gemm_warm_tiles",
+                          "zk_dac_decode_workspace", "zk_stream_workspace", "zk_dac_resunit_supported", "zk_gemm_warm_tiles",
                           "zk_torch_noise_policy", "zk_spk_conv_tiles", "zk_speaker_workspace_bytes"]
 
 

@@ -37,6 +37,21 @@ class DacSpec:
     def hop_length(self):
         return int(math.prod(self.upsampling_ratios))
 
+    @property
+    def halo_frames(self) -> int:
+        """Code frames of context a windowed decode needs on each side so that its cropped middle equals the whole
+        decode (DESIGN §6 "Streaming"). The decoder's receptive field, counted from the output back to the codes:
+        conv2 (k7) 3 samples; block i's three residual units (k7, dilations 1, 3, 9) 3 (1 + 3 + 9) = 39 positions
+        at its output rate r_i; its ConvTranspose1d (k = 2 s, stride s) 1 position at its input rate r_{i-1};
+        conv1 (k7) 3 frames."""
+        from fractions import Fraction
+        h = Fraction(3, self.hop_length) + 3
+        r = 1
+        for s in self.upsampling_ratios:
+            h += Fraction(1, r) + Fraction(39, r * s)
+            r *= s
+        return math.ceil(h)
+
     @classmethod
     def from_hf_config(cls, d: dict) -> "DacSpec":
         return cls(d.get("hidden_size", 1024), d.get("decoder_hidden_size", 1536),
@@ -364,6 +379,53 @@ class HipDacDecoder:
             call("zk_dac_tail", ptr(x), B, cl, L, ptr(self.final_alpha), ptr(self.conv2_w), ptr(self.conv2_b),
                  ptr(out), ptr(lens), scale, stream)
         return out
+
+    # decode_window runs the C ABI's zk_stream_chunk where it applies (the fp16 pipeline under c_dac); False issues
+    # the same three steps from Python (bit-identical; the reference for the test)
+    c_stream = True
+
+    @torch.inference_mode()
+    def decode_window(self, delayed: torch.Tensor, P: int, f0: int, c0: int, c1: int, f1: int, upto: int,
+                      chunk: torch.Tensor | None = None, meta: torch.Tensor | None = None):
+        """One streamed chunk of a generation that is still running: the samples of code frames [c0, c1) decoded
+        inside the window [f0, f1) (``spec.halo_frames`` of context on each side, less at the utterance's edges).
+
+        delayed: the generation's delayed codes int64 [B][K][Ld] on the device; P its audio-prefix frames; frames
+        < upto are final (engine.stream_plan). Three steps: zk_stream_window (un-delayed window codes, per-row
+        lengths and end frames) -> the decode of (codes_w, lens_w) by this decoder's pipeline, any precision ->
+        zk_stream_crop. Returns (chunk fp32 [B][(c1 - c0) hop], meta int32 [2][B] = valid samples per row, end
+        frame per row or -1 while it is live), written into ``chunk`` / ``meta`` when given."""
+        dev, hop = self.device, self.spec.hop_length
+        B, K, Ld = delayed.shape
+        stream = _lib.stream_ptr(dev)
+        if chunk is None:
+            chunk = torch.empty(B, (c1 - c0) * hop, device=dev)
+        if meta is None:
+            meta = torch.empty(2, B, dtype=torch.int32, device=dev)
+        assert delayed.is_cuda and delayed.dtype == torch.int64 and delayed.is_contiguous()
+        assert chunk.numel() >= B * (c1 - c0) * hop and meta.numel() >= 2 * B
+        if self.c_stream and self.c_dac and self.precision == "fp16" and self.cl["blocks"]:
+            d = self._dac_desc()
+            d.ncb = K
+            sd = _lib.StreamDesc(C.pointer(d), ptr(delayed), B, K, Ld, P)
+            nbytes = _lib.load().zk_stream_workspace(C.byref(sd), max(f1 - f0, 1))
+            ws = getattr(self, "_stream_ws", None)
+            if ws is None or ws.numel() < nbytes or ws.device != dev:
+                ws = self._stream_ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+            call("zk_stream_chunk", C.byref(sd), f0, c0, c1, f1, upto, ptr(ws), ws.numel(), ptr(chunk), ptr(meta[0]),
+                 ptr(meta[1]), stream)
+            return chunk, meta
+        if not (P <= f0 <= c0 < c1 <= f1 <= upto):
+            raise ValueError(f"decode_window: window not ordered P={P} <= f0={f0} <= c0={c0} < c1={c1} <= f1={f1} "
+                             f"<= upto={upto}")
+        W = f1 - f0
+        codes_w = torch.empty(B, K, W, dtype=torch.int64, device=dev)
+        lens_w = torch.empty(B, dtype=torch.int32, device=dev)
+        call("zk_stream_window", ptr(delayed), B, K, Ld, P, f0, f1, upto, ptr(codes_w), ptr(lens_w), ptr(meta[1]),
+             stream)
+        wav_w = self.decode_padded(codes_w, lens_w)
+        call("zk_stream_crop", ptr(wav_w), B, hop, f0, c0, c1, f1, ptr(meta[1]), ptr(chunk), ptr(meta[0]), stream)
+        return chunk, meta
 
     def decode_list(self, codes_list, max_batch_bytes: float = 64e9) -> list:
         """Per-utterance waveforms for a list of [9, T_i] / [1, 9, T_i] code tensors, decoded as

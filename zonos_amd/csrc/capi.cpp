@@ -31,12 +31,13 @@ extern "C" void zk_set_error(const char* fmt, ...) {
 
 extern "C" const char* zk_last_error(void) { return g_err; }
 
-extern "C" int zk_version(void) { return 1; }
+extern "C" int zk_version(void) { return 2; }
 
 // sizeof / offsetof of the by-value ABI structs, so a binding (ctypes here) can verify its
 // layout without a GPU: which = 0 zk_sampling_params, 1 zk_gen_state, 4 ZkCondSeg, 5 ZkCondPlan,
 // 6 zk_step_layer, 7 zk_step_desc, 8 zk_dac_desc; 12-25 sizes / field offsets (see the cases);
-// 26-30 zk_spk_block / zk_spk_desc; 31-32 the FP8-weight fields of zk_step_desc / zk_step_layer.
+// 26-30 zk_spk_block / zk_spk_desc; 31-32 the FP8-weight fields of zk_step_desc / zk_step_layer;
+// 33-34 zk_stream_desc.
 extern "C" long zk_abi_size(int which) {
     switch (which) {
         case 0: return (long)sizeof(zk_sampling_params);
@@ -67,6 +68,8 @@ extern "C" long zk_abi_size(int which) {
         case 30: return (long)offsetof(zk_spk_desc, lda_b);
         case 31: return (long)offsetof(zk_step_desc, w_fp8);
         case 32: return (long)offsetof(zk_step_layer, wqkv8);
+        case 33: return (long)sizeof(zk_stream_desc);
+        case 34: return (long)offsetof(zk_stream_desc, B);
         default: return -1;
     }
 }

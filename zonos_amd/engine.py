@@ -27,7 +27,9 @@ import ctypes as C
 import logging
 import math
 import os
+import weakref
 from dataclasses import dataclass
+from types import SimpleNamespace
 
 import torch
 
@@ -73,6 +75,160 @@ def check_sampling_params(spd: dict) -> None:
 N_CB = 9
 VOCAB = 1026
 ATTN_CHUNK = 256
+
+
+# ---------------------------------------------------------------------- streaming (DESIGN §6 "Streaming")
+def stream_plan(P: int, C: int, H: int, upto_prev: int, upto: int, ended: bool) -> list:
+    """The chunks to emit at a poll that found frames < ``upto`` final, the poll before having found ``upto_prev``
+    (anything <= P before the first poll): a list of windows (f0, c0, c1, f1) in absolute code frames.
+
+    Chunk j covers [c0, c1) = [P + j C, P + (j + 1) C) and is decoded inside [f0, f1) = [max(P, c0 - H),
+    min(c1 + H, upto)): H frames of context on each side (DacSpec.halo_frames), none before P -- the streamed audio
+    is the decode of the returned codes, which do not hold the audio prefix -- and none past the final frames. It is
+    ready once c1 + H <= upto. ``ended`` (the loop has stopped, ``upto`` is final) flushes every remaining frame,
+    a short last chunk included. Pure host arithmetic; every frame of [P, final upto) is covered exactly once."""
+    if C < 1 or H < 0 or P < 0:
+        raise ValueError(f"stream_plan: C={C} must be >= 1, H={H} and P={P} >= 0")
+
+    def ready(u):                # chunks j with P + (j + 1) C + H <= u
+        return max(0, (u - H - P) // C)
+
+    j1 = max(ready(upto_prev), -(-(upto - P) // C)) if ended else ready(upto)
+    out = []
+    for j in range(ready(upto_prev), j1):
+        c0 = P + j * C
+        c1 = min(c0 + C, upto)
+        out.append((max(P, c0 - H), c0, c1, min(c1 + H, upto)))
+    return out
+
+
+@dataclass
+class StreamChunk:
+    """One item of HipDecoder.stream(): ``index`` counts chunks from 0; ``frame0`` is the chunk's first code frame
+    in the coordinates of the returned codes (the audio prefix not counted); ``wavs[b]`` the fp32 [1, n_b] samples
+    of utterance b (n_b = 0 once it has ended); ``done[b]`` says that utterance b has no audio behind this chunk."""
+    index: int
+    frame0: int
+    wavs: list
+    done: list
+
+
+class _Streamer:
+    """The device side of stream(): window decodes on a second HIP stream, chunks handed out through one pinned
+    buffer. The decode of the windows a poll made ready is enqueued after the next poll's graph launch, behind an
+    event recorded after its own poll, so the decode steps never wait for the DAC; the window kernel reads final
+    columns only, which later steps do not rewrite."""
+
+    def __init__(self, decoder, B: int, C: int, to_host: bool, device):
+        self.dec, self.B, self.C, self.to_host = decoder, B, C, to_host
+        self.H = decoder.spec.halo_frames
+        self.hop = decoder.spec.hop_length
+        self.device = device
+        self.main = torch.cuda.current_stream(device)
+        self.side = torch.cuda.Stream(device)
+        self.copied = torch.cuda.Event()
+        self.meta = torch.empty(2, B, dtype=torch.int32, device=device)
+        self.pin_meta = torch.empty(2, B, dtype=torch.int32).pin_memory()
+        if to_host:
+            self.chunk = torch.empty(B * C * self.hop, device=device)
+            self.pin = torch.empty(B * C * self.hop).pin_memory()
+        self.index = 0
+        self.steps = 0               # decode steps run when the chunk last yielded became ready
+        self.upto_prev = 0
+        self.decode_events = None    # tools/stream_bench.py: a list collects (start, end) events per window
+
+    def mark(self):
+        """An event behind what the main stream holds now (the poll just launched)."""
+        ev = torch.cuda.Event()
+        ev.record(self.main)
+        return ev
+
+    def plan(self, P: int, upto: int, ended: bool, steps: int, ev) -> dict:
+        wins = stream_plan(P, self.C, self.H, self.upto_prev, upto, ended)
+        self.upto_prev = max(self.upto_prev, upto)
+        return dict(wins=wins, P=P, upto=upto, ended=ended, steps=steps, ev=ev)
+
+    def emit(self, delayed: torch.Tensor, p: dict):
+        """Decode and yield the windows of plan p, one StreamChunk each."""
+        B, hop = self.B, self.hop
+        for f0, c0, c1, f1 in p["wins"]:
+            n = B * (c1 - c0) * hop
+            with torch.cuda.stream(self.side):
+                if p["ev"] is not None:
+                    self.side.wait_event(p["ev"])
+                else:
+                    self.side.wait_stream(self.main)
+                buf = self.chunk if self.to_host else torch.empty(n, device=self.device)
+                if self.decode_events is not None:
+                    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    t0.record(self.side)
+                self.dec.decode_window(delayed, p["P"], f0, c0, c1, f1, p["upto"], chunk=buf, meta=self.meta)
+                if self.decode_events is not None:
+                    t1.record(self.side)
+                    self.decode_events.append((t0, t1))
+                if self.to_host:
+                    self.pin[:n].copy_(buf[:n], non_blocking=True)
+                self.pin_meta.copy_(self.meta, non_blocking=True)
+                self.copied.record(self.side)
+            self.copied.synchronize()
+            nb, end = self.pin_meta[0].tolist(), self.pin_meta[1].tolist()
+            src = (self.pin if self.to_host else buf)[:n].view(B, (c1 - c0) * hop)
+            wavs = [src[b:b + 1, :nb[b]].clone() if self.to_host else src[b:b + 1, :nb[b]] for b in range(B)]
+            last = p["ended"] and c1 >= p["upto"]
+            done = [last or 0 <= end[b] <= c1 for b in range(B)]
+            self.steps = p["steps"]
+            chunk = StreamChunk(self.index, c0 - p["P"], wavs, done)
+            self.index += 1
+            yield chunk
+
+    def drain(self):
+        self.side.synchronize()
+
+
+class AudioStream:
+    """What HipDecoder.stream() returns: an iterator of StreamChunk. ``steps`` is the number of decode steps that had
+    run when the chunk last yielded became ready; after exhaustion ``codes`` holds what generate() returns for the
+    same arguments. ``close()`` (or dropping the iterator, or leaving a ``with`` block) ends the generation early:
+    what is enqueued is drained and the engine is ready for the next call."""
+
+    def __init__(self, engine, run):
+        self._engine, self._run = engine, run
+        self._it = engine._decode_loop(run)
+        self._started = False
+        self.codes = None
+
+    @property
+    def steps(self) -> int:
+        return self._run.streamer.steps
+
+    def __iter__(self):
+        return self
+
+    def __next__(self) -> StreamChunk:
+        self._started = True
+        try:
+            return next(self._it)
+        except StopIteration:
+            self.codes = self._run.result
+            raise
+
+    def close(self):
+        self._it.close()
+        if not self._started:            # never iterated: the prefill is enqueued all the same
+            self._started = True
+            self._engine._finish(self._run)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 @dataclass
@@ -605,6 +761,49 @@ class HipDecoder(HipBackbone):
         batch-wide EOS protocol (model.py:376-393): they start in EOS mode with no hold-off and no
         remaining steps, so an EOS they sample never triggers the resample draw of the real rows and
         never keeps the loop running after the real rows have stopped."""
+        run = self._begin(prefix_conditioning, audio_prefix_codes, max_new_tokens, cfg_scale, batch_size,
+                          sampling_params, seed, row_base, force_full_length, callback, progress, poll_every, trace,
+                          use_graph, _after_prefill, noise, generator, pad_rows, kv_dtype, weight_dtype)
+        for _ in self._decode_loop(run):
+            pass
+        return run.result
+
+    def stream(self, prefix_conditioning: torch.Tensor, audio_prefix_codes=None, max_new_tokens: int = 86 * 30,
+               cfg_scale: float = 2.0, batch_size: int = 1, sampling_params: dict | None = None, seed: int = 0,
+               row_base: int = 0, force_full_length: bool = False, progress=None, use_graph: bool = True,
+               noise: str = "keyed", generator: torch.Generator | None = None, pad_rows: int = 0,
+               kv_dtype: str | None = None, *, weight_dtype: str | None = None, autoencoder=None,
+               chunk_frames: int = 16, to_host: bool = True) -> AudioStream:
+        """generate() that hands out audio while it runs: an iterator of StreamChunk (``chunk_frames`` code frames
+        of every utterance each, the last one shorter), decoded by ``autoencoder`` (a DACAutoencoder or a
+        HipDacDecoder) from the frames that are final at each poll. generate()'s arguments without ``callback`` /
+        ``trace``; the loop is generate()'s with ``poll_every = chunk_frames``, so the codes -- ``.codes`` of the
+        returned AudioStream after exhaustion -- and the state torch's generator is left in are generate()'s.
+
+        The chunks of a row, concatenated, are bit for bit ``autoencoder.decode(codes_row[None])[0]``: each chunk
+        is decoded inside a window with ``DacSpec.halo_frames`` frames of context on each side. That is the raw
+        decoder output: the loudness normalisation, silence trim and fades of ``codes_to_wavs`` need the whole
+        utterance and are not applied. ``to_host``: CPU tensors, copied through one pinned buffer (default), or
+        device tensors. The prefill is enqueued by this call; the first chunk is ready at the first poll with
+        chunk_frames + halo_frames final frames. Ending the iteration early is safe (AudioStream.close)."""
+        if int(chunk_frames) < 1:
+            raise ValueError(f"chunk_frames={chunk_frames} must be >= 1")
+        if autoencoder is None:
+            raise ValueError("stream() needs the autoencoder that decodes the chunks")
+        decoder = getattr(autoencoder, "decoder", autoencoder)
+        with torch.inference_mode():
+            run = self._begin(prefix_conditioning, audio_prefix_codes, max_new_tokens, cfg_scale, batch_size,
+                              sampling_params, seed, row_base, force_full_length, None, progress, int(chunk_frames),
+                              None, use_graph, None, noise, generator, pad_rows, kv_dtype, weight_dtype)
+            run.streamer = _Streamer(decoder, batch_size, int(chunk_frames), to_host, self.device)
+        out = AudioStream(self, run)
+        self._streaming = weakref.ref(out)
+        return out
+
+    def _begin(self, prefix_conditioning, audio_prefix_codes, max_new_tokens, cfg_scale, batch_size, sampling_params,
+               seed, row_base, force_full_length, callback, progress, poll_every, trace, use_graph, _after_prefill,
+               noise, generator, pad_rows, kv_dtype, weight_dtype) -> SimpleNamespace:
+        """generate() up to its decode loop: the refusals, the workspace, the prefill and the captured step."""
         assert cfg_scale != 1, "TODO: add support for cfg_scale=1"                     # model.py:247
         if batch_size * 2 != prefix_conditioning.shape[0]:                            # model.py:249-250
             raise ValueError(f"Batch size mismatch: {batch_size} * 2 != {prefix_conditioning.shape[0]}")
@@ -643,6 +842,11 @@ class HipDecoder(HipBackbone):
         Lc = int(prefix_conditioning.shape[1])
         if self._w8:
             self.quantize_weights_fp8()
+        live = getattr(self, "_streaming", None)
+        live = live() if live is not None else None
+        if live is not None:                # a stream() left unfinished works in the buffers this call takes over
+            self._streaming = None
+            live.close()
         ws = self._alloc(B, Lc, P, max_new_tokens)
         stream = _lib.stream_ptr(self.device)
         T, Ld, S = ws["T"], ws["Ld"], ws["S_pre"]
@@ -735,48 +939,87 @@ class HipDecoder(HipBackbone):
         G = max(g for g in range(1, min(self.graph_steps, per_poll) + 1) if per_poll % g == 0)
         if use_graph and trace is None:
             graph = self._capture(ws, B, st, sp, stream, G)
-        done_steps = 0
-        while True:
-            n = min(per_poll, max_steps - done_steps)
-            if n <= 0:
-                break
-            if logdbg:                      # state the step starts from (debug logging only)
-                pre = (ws["scal"].cpu(), ws["act"][0].item(), ws["rp"][0].item(), ws["eos_mode"].cpu())
-            if graph is not None:
-                call("zk_graph_launch", graph, -(-n // G), stream)
-            else:
-                for _ in range(n):
-                    self._decode_step(ws, B, st, sp, stream)
-            done_steps += n
-            if logdbg:
-                self._log_step(ws, spd, pre, force_full_length)
-            if trace is not None:
-                trace["logits"].append(ws["dbg"].clone())
-            scal = ws["scal"].cpu()
-            if eosdbg:
-                eos_prev = self._log_new_eos(ws, eos_prev, int(scal[0]) - 1)
-            if progress is not None:
-                progress.update(n)
-            if callback is not None:
-                off = int(scal[0]) - 1
-                frame = ws["delayed"][..., off:off + 1]
-                if not callback(frame, done_steps, max_steps):
-                    break
-            if trace is not None:
-                off = int(scal[0]) - 1
-                trace["tokens"].append(ws["delayed"][..., off:off + 1].clone())
-            if int(scal[3]):
-                break
-        scal = ws["scal"].cpu()
-        offset = int(scal[0]) - 1
-        if gen is not None and float(spd["temperature"]) > 0:
+        return SimpleNamespace(ws=ws, B=B, P=P, st=st, sp=sp, spd=spd, stream=stream, gen=gen,
+                               off0=off0 if gen is not None else 0, incr=incr if gen is not None else 0,
+                               force_full_length=force_full_length, callback=callback, progress=progress, trace=trace,
+                               logdbg=logdbg, eosdbg=eosdbg, eos_prev=eos_prev if eosdbg else None, per_poll=per_poll,
+                               G=G, graph=graph, max_steps=max_steps, streamer=None, result=None, finished=False)
+
+    def _finish(self, run) -> torch.Tensor:
+        """The end of a generation, run to its end or left early: waits for what is enqueued and advances the
+        torch-noise generator by the sampler calls that were made. Returns the step words."""
+        if run.streamer is not None:
+            run.streamer.drain()
+        scal = run.ws["scal"].cpu()
+        if not run.finished and run.gen is not None and float(run.spd["temperature"]) > 0:
             # sampler calls the reference made: the prefill sample, one per loop iteration
             # (scal[2] counts from 1) and one per EOS resample (scal[4]); greedy draws nothing
-            gen.set_offset(off0 + (int(scal[2]) + int(scal[4])) * incr)
-        if trace is not None:
-            trace["delayed"] = ws["delayed"].clone()
-            trace["offset"] = offset
-        return finalize(ws["delayed"], offset, P, stream)
+            run.gen.set_offset(run.off0 + (int(scal[2]) + int(scal[4])) * run.incr)
+        run.finished = True
+        return scal
+
+    @torch.inference_mode()
+    def _decode_loop(self, run):
+        """generate()'s decode loop (model.py:345-432) and output trim; leaves the codes in run.result. With a
+        streamer (stream()) it is a generator of StreamChunk: the windows a poll made ready are decoded after the
+        next poll has been launched. Without one it yields nothing and enqueues what generate() always has."""
+        ws, B, P, st, sp, spd, stream = run.ws, run.B, run.P, run.st, run.sp, run.spd, run.stream
+        callback, progress, trace, logdbg, eosdbg = run.callback, run.progress, run.trace, run.logdbg, run.eosdbg
+        per_poll, G, graph, max_steps, eos_prev, sm = run.per_poll, run.G, run.graph, run.max_steps, run.eos_prev, run.streamer
+        done_steps = 0
+        pending = None                      # stream(): the windows the last poll made ready
+        try:
+            while True:
+                n = min(per_poll, max_steps - done_steps)
+                if n <= 0:
+                    break
+                if logdbg:                      # state the step starts from (debug logging only)
+                    pre = (ws["scal"].cpu(), ws["act"][0].item(), ws["rp"][0].item(), ws["eos_mode"].cpu())
+                if graph is not None:
+                    call("zk_graph_launch", graph, -(-n // G), stream)
+                else:
+                    for _ in range(n):
+                        self._decode_step(ws, B, st, sp, stream)
+                done_steps += n
+                if sm is not None:
+                    ev = sm.mark()
+                    if pending is not None:     # behind this poll's launch: the decode steps do not wait for the DAC
+                        yield from sm.emit(ws["delayed"], pending)
+                if logdbg:
+                    self._log_step(ws, spd, pre, run.force_full_length)
+                if trace is not None:
+                    trace["logits"].append(ws["dbg"].clone())
+                scal = ws["scal"].cpu()
+                if eosdbg:
+                    eos_prev = self._log_new_eos(ws, eos_prev, int(scal[0]) - 1)
+                if progress is not None:
+                    progress.update(n)
+                if callback is not None:
+                    off = int(scal[0]) - 1
+                    frame = ws["delayed"][..., off:off + 1]
+                    if not callback(frame, done_steps, max_steps):
+                        break
+                if trace is not None:
+                    off = int(scal[0]) - 1
+                    trace["tokens"].append(ws["delayed"][..., off:off + 1].clone())
+                if sm is not None:              # frames < off - 9 are final: the count finalize() trims to
+                    pending = sm.plan(P, int(scal[0]) - 1 - N_CB, False, done_steps, ev)
+                if int(scal[3]):
+                    break
+            scal = self._finish(run)
+            offset = int(scal[0]) - 1
+            if trace is not None:
+                trace["delayed"] = ws["delayed"].clone()
+                trace["offset"] = offset
+            if sm is not None:                  # what the last poll made ready, then every remaining frame
+                if pending is not None:
+                    yield from sm.emit(ws["delayed"], dict(pending, ev=None))
+                yield from sm.emit(ws["delayed"], sm.plan(P, offset - N_CB, True, done_steps, None))
+                sm.drain()
+            run.result = finalize(ws["delayed"], offset, P, stream)
+        except GeneratorExit:                   # the consumer left early: drain, leave torch's generator right
+            self._finish(run)
+            raise
 
     def _log_new_eos(self, ws, eos_prev, off_last):
         """model.py:381's message for the rows that entered EOS mode during the last poll.

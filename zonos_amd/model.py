@@ -158,3 +158,30 @@ class Zonos:
         if prog is not None:
             prog.close()
         return out
+
+    def stream(self, prefix_conditioning: torch.Tensor, audio_prefix_codes: torch.Tensor | None = None,
+               max_new_tokens: int = 86 * 30, cfg_scale: float = 2.0, batch_size: int = 1,
+               sampling_params: dict = dict(top_p=0, top_k=0, min_p=0, linear=0.55, conf=0.4, quad=0.0,
+                                            repetition_penalty=3.0, repetition_penalty_window=2, temperature=1.0),
+               *, seed: int | None = None, row_base: int = 0, force_full_length: bool = False, pad_rows: int = 0,
+               kv_dtype: str | None = None, weight_dtype: str | None = None, autoencoder=None,
+               chunk_frames: int = 16, to_host: bool = True):
+        """generate() that hands out audio while it runs (HipDecoder.stream): an iterator of StreamChunk(index,
+        frame0, wavs, done), ``chunk_frames`` code frames per chunk, decoded by ``autoencoder`` (default:
+        ``self.autoencoder``). ``seed`` / ``row_base`` / ``pad_rows`` / ``kv_dtype`` / ``weight_dtype`` as in
+        generate(); after exhaustion ``.codes`` of the returned object holds what generate() returns.
+
+        The chunks are what ``autoencoder.decode`` yields for the returned codes, bit for bit: the loudness
+        normalisation, silence trim and fades of ``codes_to_wavs`` need the whole utterance and are not applied.
+        ``generate_sharded`` and the backbone plugins do not stream."""
+        if int(chunk_frames) < 1:
+            raise ValueError(f"chunk_frames={chunk_frames} must be >= 1")
+        noise = "torch" if seed is None else "keyed"
+        if noise == "torch" and row_base:
+            raise ValueError("row_base needs an explicit seed (the keyed noise stream)")
+        return self.engine.stream(prefix_conditioning.to(self.device), audio_prefix_codes, max_new_tokens, cfg_scale,
+                                  batch_size, sampling_params, seed=seed or 0, row_base=row_base,
+                                  force_full_length=force_full_length, noise=noise, pad_rows=pad_rows,
+                                  kv_dtype=kv_dtype, weight_dtype=weight_dtype,
+                                  autoencoder=self.autoencoder if autoencoder is None else autoencoder,
+                                  chunk_frames=chunk_frames, to_host=to_host)
