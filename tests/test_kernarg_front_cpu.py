@@ -15,7 +15,8 @@ The OTHER families were not re-ordered. Their fronts still wait for argument loa
 here as recorded values, so that they can neither grow unseen nor be mistaken for done:
   k_embed_ln 13 dw (the 14th would split a pointer), k_resid_ln / k_resid_ln_var 13 dw: `skip` at 0x50;
   k_attn_decode* 14 dw: out / skip / part (0x48-0x5f) and for the FP8 form 0x40-0x67 lie behind the preload;
-  k_gemv_f 14 dw: the LayerNorm / merge / RoPE descriptors behind 0x48;
+  k_gemv_f 14 dw: the LayerNorm / merge / RoPE descriptors behind 0x48; k_gemv_w8 (the same body behind
+  another entry kernel) 14 dw: only the merge descriptor (0x58-0x63) is waited for;
   k_mamba_step_g 14 dw: 0x38-0x4f and the step word's pointer at 0x70;
   k_sample_heads 3 dw and k_eos_step 0: zk_gen_state is passed by value, which ends the preload where the
   struct begins (k_eos_step: first argument), and the whole struct is loaded and waited for."""
@@ -50,6 +51,7 @@ OTHER = {
     ("backbone.hip", "k_attn_decode_qs"): (14, [{(0x40, 8), (0x48, 4)}]),
     ("backbone.hip", "k_attn_decode_f8"): (14, [{(0x58, 16), (0x40, 16)}]),
     ("gemm.hip", "k_gemv_f"): (14, [set(), {(0x48, 8)}, {(0x68, 32), (0x88, 16)}, {(0x58, 8), (0x60, 4)}]),
+    ("gemm.hip", "k_gemv_w8"): (14, [set(), {(0x58, 8), (0x60, 4)}]),
     ("mamba.hip", "k_mamba_step_g"): (14, [{(0x38, 8)}, {(0x38, 16), (0x48, 8), (0x70, 8)}, {(0x38, 8), (0x40, 16), (0x70, 8)}]),
     ("sampler.hip", "k_sample_heads"): (3, [{(0x60, 16), (0xb8, 8), (0x10, 16), (0x38, 32)},
                                             {(0x60, 16), (0xb0, 16), (0x10, 16), (0x38, 32)}]),

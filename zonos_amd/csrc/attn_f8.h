@@ -32,14 +32,7 @@ ZK_DEV size_t v8_off(int key, int ch) {      // channel ch of key
     const int o = key & 31, lg = o >> 3, e = o & 7, dt = ch >> 4;
     return (size_t)(key >> 5) * 4096 + ((dt >> 1) * 64 + lg * 16 + (ch & 15)) * 16 + (dt & 1) * 8 + e;
 }
-// amax = m * 2^x, m in [1, 2): e = x - 8 for m <= 1.75, else x - 7 (the smallest e with amax * 2^-e <= 448),
-// clamped to [-126, 127]; 0 for amax == 0 (kvlayout.kv_scale_exponent computes the same integer)
-ZK_DEV int kv_scale_exp(float amax) {
-    const uint32_t u = __float_as_uint(amax);
-    const int e = (int)(u >> 23) - 127 - 8 + ((u & 0x7fffffu) > 0x600000u ? 1 : 0);
-    return amax == 0.f ? 0 : max(-126, min(127, e));
-}
-ZK_DEV float kv_pow2(int e) { return __uint_as_float((uint32_t)(e + 127) << 23); }      // e in [-126, 127]
+// (the scale rule: kv_scale_exp / kv_pow2 of common.h)
 // two / four e4m3fn bytes of x * inv, round to nearest even
 ZK_DEV uint32_t quant2(float a, float b, float inv) {
     return (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(a * inv, b * inv, 0, false) & 0xffffu;

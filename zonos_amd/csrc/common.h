@@ -72,6 +72,17 @@ ZK_DEV uint4 pack8(const float* f) {
     return make_uint4(pack2(f[0], f[1]), pack2(f[2], f[3]), pack2(f[4], f[5]), pack2(f[6], f[7]));
 }
 
+// ---------------------------------------------------------------- e4m3 power-of-two scale rule
+// The one rule of the FP8 KV cache (per key) and the FP8 weights (per output row).
+// amax = m * 2^x, m in [1, 2): e = x - 8 for m <= 1.75, else x - 7 (the smallest e with amax * 2^-e <= 448),
+// clamped to [-126, 127]; 0 for amax == 0 (kvlayout.kv_scale_exponent computes the same integer)
+ZK_DEV int kv_scale_exp(float amax) {
+    const uint32_t u = __float_as_uint(amax);
+    const int e = (int)(u >> 23) - 127 - 8 + ((u & 0x7fffffu) > 0x600000u ? 1 : 0);
+    return amax == 0.f ? 0 : max(-126, min(127, e));
+}
+ZK_DEV float kv_pow2(int e) { return __uint_as_float((uint32_t)(e + 127) << 23); }      // e in [-126, 127]
+
 // ---------------------------------------------------------------- decode GEMM tile order
 // Tile (bx, bz) of linear workgroup id L (= blockIdx.x + gx * blockIdx.z) of a k_gemm_ws grid
 // gx x 1 x gz. XCD-aware order: workgroups are dispatched round-robin over the 8 XCDs (L % 8),

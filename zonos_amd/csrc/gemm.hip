@@ -633,9 +633,10 @@ __global__ __launch_bounds__(256, 1) void k_gemv_rk(const bf16_t* __restrict__ A
 // workgroup -- 4 of the 8 128-B lines of every 1 KB fragment each) so N = 2048 still gives
 // 256 workgroups.
 // mode 0: fp32 Cf[M][N]; mode 1: SwiGLU -> bf16 Cb[M][N/2]; mode 2: residual, Cb = x bf16 [M][N].
-// ZK_GF_PROF (profiling builds only): lane 0 of wave 0 of each k_gemv_f workgroup writes s_memrealtime
+// ZK_GF_PROF (profiling builds only): lane 0 of wave 0 of each workgroup writes s_memrealtime
 // stamps [entry, first MFMA issued, last MFMA issued, end] to g_gf_prof[slot][blockIdx.x][k], slot =
 // 2 * MODE + (MRG > 0) (so the launches of one kind in a step overwrite each other: the last one stays).
+// The stamps are in the shared body: k_gemv_f and k_gemv_w8 launches both stamp, into the same slots.
 #ifdef ZK_GF_PROF
 __device__ uint64_t* g_gf_prof;
 #define ZK_GF_STAMP(k)                                                                                      \
@@ -689,13 +690,62 @@ struct GfQkv {
     int H, Hkv, Smax;
 };
 
-template <int MODE, bool LN, int NTW, bool HALF, int NW, int KS, int PF, int MRG = 0, int XR = 16>
-__global__ __launch_bounds__(64 * NW, 1) void k_gemv_f(const bf16_t* __restrict__ A, long lda,
-                                                       const bf16_t* __restrict__ W, int M, int N, int K,
-                                                       const bf16_t* __restrict__ lnw, const bf16_t* __restrict__ lnb,
-                                                       float eps, float* __restrict__ Cf, bf16_t* __restrict__ Cb,
-                                                       const int32_t* skip, const float* __restrict__ mw = nullptr,
-                                                       int mhkv = 1, GfQkv qk = GfQkv{}) {
+// The weight stream is a policy: the kernel body below is written once, and the two entry kernels differ in
+// the packed image a lane's 16-byte load reads and in how its bytes become the MFMA's bf16 operand.
+//   elem, lda_t  element type of the image; type of the kernel's row-stride argument
+//   KPL          k-steps (of 32) one lane load covers
+//   KSH          log2 of the K range one wave load covers (K >> KSH wave loads per tile)
+//   EPL, EPW     elements per lane load / per wave load
+//   load         the non-temporal 16-byte load; to_bf16: the load's KPL k-steps as bf16 fragments
+struct WsBf16 {                      // zk_pack_weights: [Npad/16][K/32][lane 64][8] bf16
+    typedef bf16_t elem;
+    typedef long lda_t;
+    static constexpr bool SCALED = false;
+    static constexpr int KPL = 1, KSH = 5, EPL = 8, EPW = 512;
+    static ZK_DEV uint4 load(const elem* p) { return ldg_w(p); }
+    static ZK_DEV void to_bf16(const uint4 raw, float, uint4* b) { b[0] = raw; }
+};
+// FP8 (OCP e4m3fn) weights, opt-in (generate(weight_dtype="fp8")): the four layer GEMVs of the B <= 8 step
+// stream half the bytes. Format and packed image: zonos_amd/wlayout.py -- one power-of-two scale per output
+// row (its biased exponent byte), image [Npad/16 tiles][K/64 pairs][lane 64][q 2][8]: the bf16 fragment
+// order with the k-steps 2*pair and 2*pair + 1 side by side in a lane, so one load covers 2 k-steps (HALF:
+// 4 -- the other half's lanes read pair 2j + 1 at their neighbour's position and convert it with the
+// NEIGHBOUR's scale before the row rotation hands it over). A lane's bytes become bf16 with the row's scale
+// applied inside the hardware conversion (the scale is constant per lane: lane ln = output column), so the
+// MFMA operands are the bits of the dequantised weights and an FP8 launch returns the bits of the bf16
+// launch on pack_weights(dequantize_w_e4m3(...)).
+// In bounds: a weight load reads 16 B at ((tile * K/64 + pair) * 64 + lane') * 16 with tile clamped to
+// Npad/16 - 1, pair < K/64 (the wave's own K range) and lane' < 64: inside the Npad * K image; the scale
+// load reads byte 16 * tile + (0..15) < Npad.
+typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_w;
+// eight e4m3fn bytes (one k-step of a lane) -> eight bf16 of value q * sc, sc a power of two
+ZK_DEV uint4 w8_cvt8(uint32_t lo, uint32_t hi, float sc) {
+    const bf16x2_w a = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(lo, sc, false);
+    const bf16x2_w b = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(lo, sc, true);
+    const bf16x2_w c = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(hi, sc, false);
+    const bf16x2_w d = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(hi, sc, true);
+    return make_uint4(__builtin_bit_cast(uint32_t, a), __builtin_bit_cast(uint32_t, b), __builtin_bit_cast(uint32_t, c),
+                      __builtin_bit_cast(uint32_t, d));
+}
+struct WsE4m3 {
+    typedef uint8_t elem;
+    typedef int lda_t;               // (an int, so that the LayerNorm pointers still arrive in the preloaded dwords)
+    static constexpr bool SCALED = true;
+    static constexpr int KPL = 2, KSH = 6, EPL = 16, EPW = 1024;
+    static ZK_DEV uint4 load(const elem* p) {
+        return __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p)));
+    }
+    static ZK_DEV void to_bf16(const uint4 raw, float sc, uint4* b) {
+        b[0] = w8_cvt8(raw.x, raw.y, sc);
+        b[1] = w8_cvt8(raw.z, raw.w, sc);
+    }
+};
+
+template <class WS, int MODE, bool LN, int NTW, bool HALF, int NW, int KS, int PF, int MRG, int XR>
+ZK_DEV void gemv_body(const bf16_t* __restrict__ A, typename WS::lda_t lda, const typename WS::elem* __restrict__ W,
+                      const uint8_t* __restrict__ wsc, int M, int N, int K, const bf16_t* __restrict__ lnw,
+                      const bf16_t* __restrict__ lnb, float eps, float* __restrict__ Cf, bf16_t* __restrict__ Cb,
+                      const int32_t* skip, const float* __restrict__ mw, int mhkv, const GfQkv& qk) {
     static_assert(MODE != 3 || (LN && NTW == 1 && !HALF && XR == 2), "qkv RoPE epilogue: the B = 1 in_proj");
     ZK_GF_STAMP(0);
     static_assert(!HALF || NTW == 1, "HALF is one half tile");
@@ -707,9 +757,10 @@ __global__ __launch_bounds__(64 * NW, 1) void k_gemv_f(const bf16_t* __restrict_
     constexpr int XSTR = XC ? NW * KS * 32 + 8 : GF_XS;              // LDS image row stride (bf16)
     constexpr int XCN = XC ? KS * 32 * 2 / 512 : 1;                  // XC: 16-B loads per lane (2 rows)
     static_assert(!XC || (KS * 32 * 2) % 512 == 0, "XC: whole 512-element load rounds per wave");
-    constexpr int KPL = HALF ? 2 : 1;                                // k-steps per weight load
+    constexpr int KPL = WS::KPL * (HALF ? 2 : 1);                    // k-steps per weight load
     constexpr int NL = KS / KPL;                                     // weight loads per wave and tile
-    static_assert(NL * KPL == KS, "HALF pairs k-steps");
+    static_assert(NL * KPL == KS && PF <= NL, "whole loads of (HALF: paired) k-steps");
+    constexpr int LSTR = WS::EPW * (HALF ? 2 : 1);                   // elements between a lane's loads
     constexpr int MR = (XR + NW - 1) / NW;                           // LN rows per wave
     static_assert(!MRG || XR == 2, "merge prologue: M <= 2");
     __shared__ __attribute__((aligned(16))) uint4 xs[XS ? XR * XSTR / 8 : 1];
@@ -728,6 +779,13 @@ __global__ __launch_bounds__(64 * NW, 1) void k_gemv_f(const bf16_t* __restrict_
     // the prologue (LN rows) / epilogue (residual) data must be older than the weight prefetch
     // to be waited for without draining it. The empty asm with a memory clobber + sched_barrier
     // keep the compiler from moving these loads behind the prefetch.
+    // A scaled stream's scale byte goes with them (the column whose bytes the lane loads: its own, or in the
+    // other half of a half tile its neighbour's).
+    uint32_t scb[NTW] = {};
+    if constexpr (WS::SCALED) {
+#pragma unroll
+        for (int tt = 0; tt < NTW; ++tt) scb[tt] = wsc[min(nt0 + tt, ntiles - 1) * 16 + (wl ? ln : (ln ^ 8))];
+    }
     constexpr int NJ = LN ? 4 : 1;                                   // 16-B chunks per lane per row
     uint4 xv[LN ? MR : 1][NJ] = {}, wv[NJ] = {}, bv[NJ] = {};
     // B = 1: only the waves that normalise a row (w < M) load the row and the LayerNorm
@@ -790,17 +848,18 @@ __global__ __launch_bounds__(64 * NW, 1) void k_gemv_f(const bf16_t* __restrict_
     asm volatile("" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
 
-    const int lsrc = wl ? lane * 8 : 512 + (lane ^ 8) * 8;          // HALF: k-step 2j+1 for the other half
-    const bf16_t* wp[NTW];
+    // HALF: the next wave load (bf16: k-step 2j+1) for the other half
+    const int lsrc = wl ? lane * WS::EPL : WS::EPW + (lane ^ 8) * WS::EPL;
+    const typename WS::elem* wp[NTW];
 #pragma unroll
     for (int tt = 0; tt < NTW; ++tt)
-        wp[tt] = W + ((size_t)min(nt0 + tt, ntiles - 1) * (K >> 5) + (kbeg >> 5)) * 512 + lsrc;
+        wp[tt] = W + ((size_t)min(nt0 + tt, ntiles - 1) * (K >> WS::KSH) + (kbeg >> WS::KSH)) * WS::EPW + lsrc;
     const bf16_t* ap = A + (size_t)mrow * lda + kbeg + lg * 8;
     constexpr int U = PF + 1;
     uint4 wr[U][NTW], ar[U][KPL];
     auto issue = [&](int ls, int slot) {
 #pragma unroll
-        for (int tt = 0; tt < NTW; ++tt) wr[slot][tt] = ldg_w(wp[tt] + ls * 512 * KPL);
+        for (int tt = 0; tt < NTW; ++tt) wr[slot][tt] = WS::load(wp[tt] + ls * LSTR);
         if constexpr (!XS) {
 #pragma unroll
             for (int q = 0; q < KPL; ++q) ar[slot][q] = *reinterpret_cast<const uint4*>(ap + (ls * KPL + q) * 32);
@@ -833,6 +892,10 @@ __global__ __launch_bounds__(64 * NW, 1) void k_gemv_f(const bf16_t* __restrict_
 #pragma unroll
                 for (int tt = 0; tt < NTW; ++tt) keep_live(wr[p][tt]);
             }
+        if constexpr (WS::SCALED) {
+#pragma unroll
+            for (int tt = 0; tt < NTW; ++tt) asm volatile("" ::"v"(scb[tt]));
+        }
         if constexpr (LN) {
 #pragma unroll
             for (int j = 0; j < NJ; ++j) {
@@ -946,6 +1009,9 @@ __global__ __launch_bounds__(64 * NW, 1) void k_gemv_f(const bf16_t* __restrict_
         // each wave reads back only the dims it wrote (its own K range): no workgroup barrier
     }
 
+    float sc[NTW];                                                   // (scaled stream: 2^(byte - 127))
+#pragma unroll
+    for (int tt = 0; tt < NTW; ++tt) sc[tt] = __uint_as_float((scb[tt] & 0xffu) << 23);
     f32x4 acc[NTW];
 #pragma unroll
     for (int tt = 0; tt < NTW; ++tt) acc[tt] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -954,6 +1020,9 @@ __global__ __launch_bounds__(64 * NW, 1) void k_gemv_f(const bf16_t* __restrict_
     for (int ls = 0; ls < NL; ++ls) {
         if (ls + PF < NL) issue(ls + PF, (ls + PF) % U);
         __builtin_amdgcn_sched_barrier(0);
+        uint4 bk[NTW][WS::KPL];                                      // the k-steps of the lane's own load
+#pragma unroll
+        for (int tt = 0; tt < NTW; ++tt) WS::to_bf16(wr[ls % U][tt], sc[tt], bk[tt]);
 #pragma unroll
         for (int q = 0; q < KPL; ++q) {
             uint4 a;
@@ -961,7 +1030,8 @@ __global__ __launch_bounds__(64 * NW, 1) void k_gemv_f(const bf16_t* __restrict_
             else a = ar[ls % U][q];
 #pragma unroll
             for (int tt = 0; tt < NTW; ++tt) {
-                const uint4 b = q == 0 ? wr[ls % U][tt] : row_ror4<8>(wr[ls % U][tt]);
+                const uint4 own = bk[tt][q % WS::KPL];
+                const uint4 b = q < WS::KPL ? own : row_ror4<8>(own);   // HALF: the neighbour's k-steps
                 acc[tt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_frag(a), as_frag(b), acc[tt], 0, 0, 0);
             }
         }
@@ -1030,6 +1100,29 @@ __global__ __launch_bounds__(64 * NW, 1) void k_gemv_f(const bf16_t* __restrict_
         if (MODE == 0) Cf[(size_t)m * N + n_out] = sum[i];
         else Cb[(size_t)m * N + n_out] = f2bf(bf2f(rv[i]) + round_bf(sum[i]));
     }
+}
+
+// The two entry kernels only forward. (k_gemv_w8: `W, wsc` ahead of an int lda, which keeps the LayerNorm
+// pointers inside the 14 preloaded argument dwords.)
+template <int MODE, bool LN, int NTW, bool HALF, int NW, int KS, int PF, int MRG = 0, int XR = 16>
+__global__ __launch_bounds__(64 * NW, 1) void k_gemv_f(const bf16_t* __restrict__ A, long lda,
+                                                       const bf16_t* __restrict__ W, int M, int N, int K,
+                                                       const bf16_t* __restrict__ lnw, const bf16_t* __restrict__ lnb,
+                                                       float eps, float* __restrict__ Cf, bf16_t* __restrict__ Cb,
+                                                       const int32_t* skip, const float* __restrict__ mw = nullptr,
+                                                       int mhkv = 1, GfQkv qk = GfQkv{}) {
+    gemv_body<WsBf16, MODE, LN, NTW, HALF, NW, KS, PF, MRG, XR>(A, lda, W, nullptr, M, N, K, lnw, lnb, eps, Cf, Cb, skip,
+                                                                mw, mhkv, qk);
+}
+template <int MODE, bool LN, int NTW, bool HALF, int NW, int KS, int PF, int MRG = 0, int XR = 16>
+__global__ __launch_bounds__(64 * NW, 1) void k_gemv_w8(const bf16_t* __restrict__ A, const uint8_t* __restrict__ W,
+                                                        const uint8_t* __restrict__ wsc, int lda, int M, int N, int K,
+                                                        const bf16_t* __restrict__ lnw, const bf16_t* __restrict__ lnb,
+                                                        float eps, float* __restrict__ Cf, bf16_t* __restrict__ Cb,
+                                                        const int32_t* skip, const float* __restrict__ mw = nullptr,
+                                                        int mhkv = 1, GfQkv qk = GfQkv{}) {
+    gemv_body<WsE4m3, MODE, LN, NTW, HALF, NW, KS, PF, MRG, XR>(A, lda, W, wsc, M, N, K, lnw, lnb, eps, Cf, Cb, skip, mw,
+                                                                mhkv, qk);
 }
 
 // nn.Linear [N][K] -> fragment-packed [Npad/16][K/32][64][8] (rows >= N zero)
@@ -1224,14 +1317,17 @@ int gemm_launch(const GemmPlan& p, const void* A, long lda, const void* W, int M
 }
 
 // k_gemv_f layouts: 0 half a tile per workgroup, 1 one tile, 2 two tiles. The template selectors of a
-// launch follow from (layout, LayerNorm prologue, KSW = K / 32 k-steps of the workgroup, XR rows).
+// launch follow from (layout, LayerNorm prologue, KSW = K / 32 k-steps of the workgroup, XR rows) and the
+// weight stream's k-steps per lane load (1 bf16, 2 e4m3): both streams get the same tiles per workgroup, waves
+// and k-steps per wave (the arithmetic); the prefetch depth counts the stream's own loads (of kpl k-steps,
+// HALF: 2 kpl), so an FP8 launch keeps all of a wave's loads in flight wherever the bf16 launch does.
 struct GfForm { int ntw; bool half; int nw, ks, pf; };
 constexpr bool operator==(const GfForm& a, const GfForm& b) {
     return a.ntw == b.ntw && a.half == b.half && a.nw == b.nw && a.ks == b.ks && a.pf == b.pf;
 }
-constexpr GfForm gf_form(int lay, bool ln, int ksw, int xr) {
+constexpr GfForm gf_form(int lay, bool ln, int ksw, int xr, int kpl = WsBf16::KPL) {
     const bool half = lay == 0;
-    const int nw = half ? ZK_GF_NWH : ZK_GF_NW, ks = ksw / nw, nl = half ? ks / 2 : ks;
+    const int nw = half ? ZK_GF_NWH : ZK_GF_NW, ks = ksw / nw, nl = ks / (half ? 2 * kpl : kpl);
     const int pb = (xr == 2 && ln && lay == 1) ? ZK_GF_PFLN : ZK_GF_PF;
     return GfForm{lay == 2 ? 2 : 1, half, nw, ks, nl < pb ? nl : pb};
 }
@@ -1297,32 +1393,136 @@ extern "C" int zk_gemm_warm_tiles(int M, int N, int K, int nsplit, int mode, int
     return hi;
 }
 
-extern "C" int zk_gemv_fused(const void* A, long lda, const void* W, int M, int N, int K, int mode,
-                             const void* ln_w, const void* ln_b, float eps, float* Cf, void* Cb,
-                             const int32_t* skip_flag, void* stream) {
-    ZK_REQUIRE(M >= 1 && M <= 16 && N > 0, "zk_gemv_fused: M=%d (1..16) N=%d", M, N);
-    ZK_REQUIRE(K == 2048 || K == 4096 || K == 8192, "zk_gemv_fused: K=%d (2048, 4096 or 8192)", K);
-    ZK_REQUIRE(lda >= K && lda % 8 == 0, "zk_gemv_fused: lda=%ld", lda);
-    ZK_REQUIRE(mode >= 0 && mode <= 2, "zk_gemv_fused: mode %d", mode);
-    ZK_REQUIRE(mode != 1 || N % 16 == 0, "zk_gemv_fused: SwiGLU needs N %% 16 == 0");
-    ZK_REQUIRE((ln_w == nullptr) == (ln_b == nullptr), "zk_gemv_fused: LN needs both w and b");
-    ZK_REQUIRE(ln_w == nullptr || K == 2048, "zk_gemv_fused: LN prologue needs K = 2048 (K=%d)", K);
-    ZK_REQUIRE(mode == 0 ? Cf != nullptr : Cb != nullptr, "zk_gemv_fused: missing output");
+// Each small-batch GEMV entry and its _w8 twin are one function over the weight stream WS: `who` is the
+// called entry's name (for its messages), W the packed image, wsc the scale bytes of a scaled stream (else
+// unused). gf_launch starts WS's entry kernel (k_gemv_f / k_gemv_w8: their argument orders).
+namespace {
+
+template <class WS, int MODE, bool LN, int NTW, bool HALF, int NW, int KS, int PF, int MRG, int XR>
+void gf_launch(int grid, int block, void* stream, const void* A, long lda, const void* W, const void* wsc, int M, int N,
+               int K, const void* ln_w, const void* ln_b, float eps, float* Cf, void* Cb, const int32_t* skip,
+               const float* mw, int mhkv, GfQkv qk = GfQkv{}) {
+    if constexpr (WS::SCALED)
+        hipLaunchKernelGGL((k_gemv_w8<MODE, LN, NTW, HALF, NW, KS, PF, MRG, XR>), dim3(grid), dim3(block), 0,
+                           (hipStream_t)stream, (const bf16_t*)A, (const uint8_t*)W, (const uint8_t*)wsc, (int)lda, M, N,
+                           K, (const bf16_t*)ln_w, (const bf16_t*)ln_b, eps, Cf, (bf16_t*)Cb, skip, mw, mhkv, qk);
+    else
+        hipLaunchKernelGGL((k_gemv_f<MODE, LN, NTW, HALF, NW, KS, PF, MRG, XR>), dim3(grid), dim3(block), 0,
+                           (hipStream_t)stream, (const bf16_t*)A, lda, (const bf16_t*)W, M, N, K, (const bf16_t*)ln_w,
+                           (const bf16_t*)ln_b, eps, Cf, (bf16_t*)Cb, skip, mw, mhkv, qk);
+}
+
+template <class WS>
+int gemv_fused(const char* who, const void* A, long lda, const void* W, const void* wsc, int M, int N, int K, int mode,
+               const void* ln_w, const void* ln_b, float eps, float* Cf, void* Cb, const int32_t* skip_flag,
+               void* stream) {
+    ZK_REQUIRE(M >= 1 && M <= 16 && N > 0, "%s: M=%d (1..16) N=%d", who, M, N);
+    ZK_REQUIRE(K == 2048 || K == 4096 || K == 8192, "%s: K=%d (2048, 4096 or 8192)", who, K);
+    // (a scaled stream's kernel takes lda as an int)
+    ZK_REQUIRE(lda >= K && lda % 8 == 0 && (!WS::SCALED || lda <= (1L << 30)), "%s: lda=%ld", who, lda);
+    ZK_REQUIRE(mode >= 0 && mode <= 2, "%s: mode %d", who, mode);
+    ZK_REQUIRE(mode != 1 || N % 16 == 0, "%s: SwiGLU needs N %% 16 == 0", who);
+    ZK_REQUIRE((ln_w == nullptr) == (ln_b == nullptr), "%s: LN needs both w and b", who);
+    ZK_REQUIRE(ln_w == nullptr || K == 2048, "%s: LN prologue needs K = 2048 (K=%d)", who, K);
+    ZK_REQUIRE(mode == 0 ? Cf != nullptr : Cb != nullptr, "%s: missing output", who);
+    ZK_REQUIRE(!WS::SCALED || (W != nullptr && wsc != nullptr), "%s: missing weight image or scales", who);
     const GemvPlan p = gemv_plan(M, N, K, mode, ln_w != nullptr);
     bool launched = false;
     pick([&](auto mode_, auto ln, auto lay, auto ksw, auto xr) {
         if constexpr (gf_has(mode_(), ln() != 0, lay(), ksw())) {
-            constexpr GfForm F = gf_form(lay(), ln() != 0, ksw(), xr());
-            hipLaunchKernelGGL((k_gemv_f<mode_(), ln() != 0, F.ntw, F.half, F.nw, F.ks, F.pf, 0, xr()>), dim3(p.grid),
-                               dim3(p.block), 0, (hipStream_t)stream, (const bf16_t*)A, lda, (const bf16_t*)W, M, N, K,
-                               (const bf16_t*)ln_w, (const bf16_t*)ln_b, eps, Cf, (bf16_t*)Cb, skip_flag, nullptr, 1);
+            constexpr GfForm F = gf_form(lay(), ln() != 0, ksw(), xr(), WS::KPL);
+            gf_launch<WS, mode_(), ln() != 0, F.ntw, F.half, F.nw, F.ks, F.pf, 0, xr()>(
+                p.grid, p.block, stream, A, lda, W, wsc, M, N, K, ln_w, ln_b, eps, Cf, Cb, skip_flag, nullptr, 1);
             launched = true;
         }
     }, mode, Ints<0, 1, 2>{}, ln_w != nullptr, Ints<0, 1>{}, p.lay, Ints<0, 1, 2>{}, p.ksw, Ints<64, 128, 256>{}, p.xr,
          Ints<2, 16>{});
-    ZK_REQUIRE(launched, "zk_gemv_fused: no kernel for K=%d", K);
-    ZK_CHECK_LAUNCH("zk_gemv_fused");
+    ZK_REQUIRE(launched, "%s: no kernel for K=%d", who, K);
+    ZK_CHECK_LAUNCH(who);
     return 0;
+}
+
+template <class WS>
+int gemv_qkv_rope(const char* who, const void* x, const void* W, const void* wsc, int M, int H, int Hkv, int hd,
+                  const void* ln_w, const void* ln_b, float eps, void* q_out, void* k_cache, void* vt_cache, int Smax,
+                  const int32_t* pos_dev, const float* freqs, const int32_t* skip_flag, void* stream) {
+    ZK_REQUIRE(M >= 1 && M <= 2, "%s: M=%d (1..2)", who, M);
+    ZK_REQUIRE(hd == 128 && H % Hkv == 0 && H / Hkv <= AT_G, "%s: H=%d Hkv=%d hd=%d", who, H, Hkv, hd);
+    const int K = H * hd, N = (H + 2 * Hkv) * hd;
+    ZK_REQUIRE(K == 2048, "%s: d_model %d (2048 only: the LayerNorm prologue)", who, K);
+    ZK_REQUIRE(x && W && (!WS::SCALED || wsc) && ln_w && ln_b && q_out && k_cache && vt_cache && pos_dev && freqs,
+               "%s: null argument", who);
+    ZK_REQUIRE(Smax > 0 && Smax % 32 == 0, "%s: Smax=%d", who, Smax);
+    const GfQkv qk{(bf16_t*)k_cache, (bf16_t*)vt_cache, pos_dev, freqs, H, Hkv, Smax};
+    // the epilogue rotates column pairs inside one whole tile: the one-tile layout, which the plan gives
+    // every N this entry accepts (at most 48 heads of 128 columns: 384 tiles, with the LayerNorm prologue)
+    const GemvPlan p = gemv_plan(M, N, K, 3, true);
+    ZK_REQUIRE(p.lay == 1 && p.xr == 2, "%s: N=%d is not a one-tile GEMV", who, N);
+    constexpr GfForm F = gf_form(1, true, 64, 2, WS::KPL);
+    gf_launch<WS, 3, true, F.ntw, F.half, F.nw, F.ks, F.pf, 0, 2>(p.grid, p.block, stream, x, (long)K, W, wsc, M, N, K,
+                                                                  ln_w, ln_b, eps, nullptr, q_out, skip_flag, nullptr, 1,
+                                                                  qk);
+    ZK_CHECK_LAUNCH(who);
+    return 0;
+}
+
+template <class WS>
+int gemv_attn_out(const char* who, const float* work, int nsplit, int Hkv, const void* W, const void* wsc, int M, int N,
+                  int K, void* x, const int32_t* skip_flag, void* stream) {
+    ZK_REQUIRE(M >= 1 && M <= 2, "%s: M=%d (1..2)", who, M);
+    ZK_REQUIRE(K == 2048 && N > 0 && N % 16 == 0, "%s: K=%d (2048) N=%d", who, K, N);
+    ZK_REQUIRE(Hkv >= 1 && (K / 128) % Hkv == 0 && (K / 128) / Hkv <= GF_AT_G, "%s: Hkv=%d", who, Hkv);
+    ZK_REQUIRE(work != nullptr && x != nullptr && (!WS::SCALED || (W != nullptr && wsc != nullptr)),
+               "%s: null buffer", who);
+    // The merge prologue needs half tiles and 8 K-range waves (of 8 k-steps, every load of a wave in flight), at
+    // every N and whatever ZK_GF_NWH / ZK_GF_PF say: the form of the residual GEMV (zk_gemv_fused mode 2,
+    // M <= 2, N < 4096) at the default switches.
+    constexpr GfForm F{1, true, 8, 8, 8 / (2 * WS::KPL)};
+    static_assert(ZK_GF_NWH != 8 || ZK_GF_PF < F.pf || F == gf_form(0, false, 64, 2, WS::KPL), "the merge GEMV's layout");
+    const bool listed = pick([&](auto ns) {
+        gf_launch<WS, 2, false, F.ntw, F.half, F.nw, F.ks, F.pf, ns(), 2>(
+            gf_grid(0, (N + 15) / 16), 64 * F.nw, stream, work, (long)K, W, wsc, M, N, K, nullptr, nullptr, 0.f, nullptr,
+            x, skip_flag, work, Hkv);
+    }, nsplit, Ints<2, 4, 8, 16>{});
+    ZK_REQUIRE(listed, "%s: nsplit=%d (2, 4, 8 or 16)", who, nsplit);
+    ZK_CHECK_LAUNCH(who);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int zk_gemv_fused(const void* A, long lda, const void* W, int M, int N, int K, int mode,
+                             const void* ln_w, const void* ln_b, float eps, float* Cf, void* Cb,
+                             const int32_t* skip_flag, void* stream) {
+    return gemv_fused<WsBf16>("zk_gemv_fused", A, lda, W, nullptr, M, N, K, mode, ln_w, ln_b, eps, Cf, Cb, skip_flag,
+                              stream);
+}
+extern "C" int zk_gemv_fused_w8(const void* A, long lda, const void* W8, const void* w_scale, int M, int N, int K,
+                                int mode, const void* ln_w, const void* ln_b, float eps, float* Cf, void* Cb,
+                                const int32_t* skip_flag, void* stream) {
+    return gemv_fused<WsE4m3>("zk_gemv_fused_w8", A, lda, W8, w_scale, M, N, K, mode, ln_w, ln_b, eps, Cf, Cb,
+                              skip_flag, stream);
+}
+extern "C" int zk_gemv_qkv_rope(const void* x, const void* W, int M, int H, int Hkv, int hd, const void* ln_w,
+                                const void* ln_b, float eps, void* q_out, void* k_cache, void* vt_cache, int Smax,
+                                const int32_t* pos_dev, const float* freqs, const int32_t* skip_flag, void* stream) {
+    return gemv_qkv_rope<WsBf16>("zk_gemv_qkv_rope", x, W, nullptr, M, H, Hkv, hd, ln_w, ln_b, eps, q_out, k_cache,
+                                 vt_cache, Smax, pos_dev, freqs, skip_flag, stream);
+}
+extern "C" int zk_gemv_qkv_rope_w8(const void* x, const void* W8, const void* w_scale, int M, int H, int Hkv, int hd,
+                                   const void* ln_w, const void* ln_b, float eps, void* q_out, void* k_cache,
+                                   void* vt_cache, int Smax, const int32_t* pos_dev, const float* freqs,
+                                   const int32_t* skip_flag, void* stream) {
+    return gemv_qkv_rope<WsE4m3>("zk_gemv_qkv_rope_w8", x, W8, w_scale, M, H, Hkv, hd, ln_w, ln_b, eps, q_out, k_cache,
+                                 vt_cache, Smax, pos_dev, freqs, skip_flag, stream);
+}
+extern "C" int zk_gemv_attn_out(const float* work, int nsplit, int Hkv, const void* W, int M, int N, int K,
+                                void* x, const int32_t* skip_flag, void* stream) {
+    return gemv_attn_out<WsBf16>("zk_gemv_attn_out", work, nsplit, Hkv, W, nullptr, M, N, K, x, skip_flag, stream);
+}
+extern "C" int zk_gemv_attn_out_w8(const float* work, int nsplit, int Hkv, const void* W8, const void* w_scale, int M,
+                                   int N, int K, void* x, const int32_t* skip_flag, void* stream) {
+    return gemv_attn_out<WsE4m3>("zk_gemv_attn_out_w8", work, nsplit, Hkv, W8, w_scale, M, N, K, x, skip_flag, stream);
 }
 
 #ifdef ZK_GF_PROF
@@ -1331,438 +1531,9 @@ extern "C" int zk_gf_prof_set(uint64_t* p) {
 }
 #endif
 
-extern "C" int zk_gemv_qkv_rope(const void* x, const void* W, int M, int H, int Hkv, int hd, const void* ln_w,
-                                const void* ln_b, float eps, void* q_out, void* k_cache, void* vt_cache, int Smax,
-                                const int32_t* pos_dev, const float* freqs, const int32_t* skip_flag, void* stream) {
-    ZK_REQUIRE(M >= 1 && M <= 2, "zk_gemv_qkv_rope: M=%d (1..2)", M);
-    ZK_REQUIRE(hd == 128 && H % Hkv == 0 && H / Hkv <= AT_G, "zk_gemv_qkv_rope: H=%d Hkv=%d hd=%d", H, Hkv, hd);
-    const int K = H * hd, N = (H + 2 * Hkv) * hd;
-    ZK_REQUIRE(K == 2048, "zk_gemv_qkv_rope: d_model %d (2048 only: the LayerNorm prologue)", K);
-    ZK_REQUIRE(x && W && ln_w && ln_b && q_out && k_cache && vt_cache && pos_dev && freqs,
-               "zk_gemv_qkv_rope: null argument");
-    ZK_REQUIRE(Smax > 0 && Smax % 32 == 0, "zk_gemv_qkv_rope: Smax=%d", Smax);
-    const GfQkv qk{(bf16_t*)k_cache, (bf16_t*)vt_cache, pos_dev, freqs, H, Hkv, Smax};
-    // the epilogue rotates column pairs inside one whole tile: the one-tile layout, which the plan gives
-    // every N this entry accepts (at most 48 heads of 128 columns: 384 tiles, with the LayerNorm prologue)
-    const GemvPlan p = gemv_plan(M, N, K, 3, true);
-    ZK_REQUIRE(p.lay == 1 && p.xr == 2, "zk_gemv_qkv_rope: N=%d is not a one-tile GEMV", N);
-    constexpr GfForm F = gf_form(1, true, 64, 2);
-    hipLaunchKernelGGL((k_gemv_f<3, true, F.ntw, F.half, F.nw, F.ks, F.pf, 0, 2>), dim3(p.grid), dim3(p.block), 0,
-                       (hipStream_t)stream, (const bf16_t*)x, (long)K, (const bf16_t*)W, M, N, K,
-                       (const bf16_t*)ln_w, (const bf16_t*)ln_b, eps, nullptr, (bf16_t*)q_out, skip_flag, nullptr, 1,
-                       qk);
-    ZK_CHECK_LAUNCH("zk_gemv_qkv_rope");
-    return 0;
-}
-
-extern "C" int zk_gemv_attn_out(const float* work, int nsplit, int Hkv, const void* W, int M, int N, int K,
-                                void* x, const int32_t* skip_flag, void* stream) {
-    ZK_REQUIRE(M >= 1 && M <= 2, "zk_gemv_attn_out: M=%d (1..2)", M);
-    ZK_REQUIRE(K == 2048 && N > 0 && N % 16 == 0, "zk_gemv_attn_out: K=%d (2048) N=%d", K, N);
-    ZK_REQUIRE(Hkv >= 1 && (K / 128) % Hkv == 0 && (K / 128) / Hkv <= GF_AT_G, "zk_gemv_attn_out: Hkv=%d", Hkv);
-    ZK_REQUIRE(work != nullptr && x != nullptr, "zk_gemv_attn_out: null buffer");
-    // The merge prologue needs half tiles and 8 K-range waves, at every N and whatever ZK_GF_NWH / ZK_GF_PF
-    // say: the form of the residual GEMV (zk_gemv_fused mode 2, M <= 2, N < 4096) at the default switches.
-    constexpr GfForm F{1, true, 8, 8, 4};
-    static_assert(ZK_GF_NWH != 8 || ZK_GF_PF < 4 || F == gf_form(0, false, 64, 2), "zk_gemv_attn_out's layout");
-    const bool listed = pick([&](auto ns) {
-        hipLaunchKernelGGL((k_gemv_f<2, false, F.ntw, F.half, F.nw, F.ks, F.pf, ns(), 2>),
-                           dim3(gf_grid(0, (N + 15) / 16)), dim3(64 * F.nw), 0, (hipStream_t)stream,
-                           reinterpret_cast<const bf16_t*>(work), (long)K, (const bf16_t*)W, M, N, K, nullptr, nullptr,
-                           0.f, nullptr, (bf16_t*)x, skip_flag, work, Hkv);
-    }, nsplit, Ints<2, 4, 8, 16>{});
-    ZK_REQUIRE(listed, "zk_gemv_attn_out: nsplit=%d (2, 4, 8 or 16)", nsplit);
-    ZK_CHECK_LAUNCH("zk_gemv_attn_out");
-    return 0;
-}
-
-// ------------------------------------------------------------------ FP8 (e4m3fn) weights, small-batch GEMVs
-// Opt-in (generate(weight_dtype="fp8")): the four layer GEMVs of the B <= 8 step stream half the bytes.
-// Format and packed image: zonos_amd/wlayout.py -- e4m3fn bytes, one power-of-two scale per output row (its
-// biased exponent byte), image [Npad/16 tiles][K/64 pairs][lane 64][q 2][8]: the bf16 fragment order with the
-// k-steps 2*pair and 2*pair + 1 side by side in a lane, so every load is 16 B per lane.
-// k_gemv_w8 is k_gemv_f with the weight stream replaced: the same workgroup -> tile map, K split over the
-// waves, prologues, MFMA sequence per accumulator (k-steps in ascending order), cross-wave sum and
-// epilogues, for the form gf_form gives the bf16 launch of the same shape. A lane's bytes become bf16 with
-// the row's scale applied inside the hardware conversion (the scale is constant per lane: lane ln = output
-// column), so the MFMA operands are the bits of the dequantised weights and an FP8 launch returns the bits
-// of the bf16 launch on pack_weights(dequantize_w_e4m3(...)).
-// One load covers 2 k-steps (HALF: 4 -- the owning lanes read pair 2j, the other half's lanes pair 2j + 1
-// at their neighbour's position, lane ^ 8, converted with the NEIGHBOUR's scale; the DPP row rotation by 8
-// then hands the k-steps 4j + 2, 4j + 3 to the owning lanes).
-// In bounds: a weight load reads 16 B at ((tile * K/64 + pair) * 64 + lane') * 16 with tile clamped to
-// Npad/16 - 1, pair < K/64 (the wave's own K range) and lane' < 64: inside the Npad * K image; the scale
-// load reads byte 16 * tile + (0..15) < Npad.
+// ------------------------------------------------------------------ FP8 (e4m3fn) weights: the packer
+// (the stream itself: WsE4m3 above)
 namespace {
-
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_w;
-
-ZK_DEV uint4 ldg_w8(const uint8_t* p) {
-    return __builtin_bit_cast(uint4, __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p)));
-}
-// the scale rule of the FP8 KV cache (attn_f8.h kv_scale_exp; kvlayout.kv_scale_exponent on the host)
-ZK_DEV int w8_scale_exp(float amax) {
-    const uint32_t u = __float_as_uint(amax);
-    const int e = (int)(u >> 23) - 127 - 8 + ((u & 0x7fffffu) > 0x600000u ? 1 : 0);
-    return amax == 0.f ? 0 : max(-126, min(127, e));
-}
-// eight e4m3fn bytes (one k-step of a lane) -> eight bf16 of value q * sc, sc a power of two
-ZK_DEV uint4 w8_cvt8(uint32_t lo, uint32_t hi, float sc) {
-    const bf16x2_w a = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(lo, sc, false);
-    const bf16x2_w b = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(lo, sc, true);
-    const bf16x2_w c = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(hi, sc, false);
-    const bf16x2_w d = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(hi, sc, true);
-    return make_uint4(__builtin_bit_cast(uint32_t, a), __builtin_bit_cast(uint32_t, b), __builtin_bit_cast(uint32_t, c),
-                      __builtin_bit_cast(uint32_t, d));
-}
-
-// (lda is an int here so that the LayerNorm pointers still arrive in the preloaded argument dwords)
-template <int MODE, bool LN, int NTW, bool HALF, int NW, int KS, int PF, int MRG = 0, int XR = 16>
-__global__ __launch_bounds__(64 * NW, 1) void k_gemv_w8(const bf16_t* __restrict__ A, const uint8_t* __restrict__ W,
-                                                        const uint8_t* __restrict__ wsc, int lda, int M, int N, int K,
-                                                        const bf16_t* __restrict__ lnw, const bf16_t* __restrict__ lnb,
-                                                        float eps, float* __restrict__ Cf, bf16_t* __restrict__ Cb,
-                                                        const int32_t* skip, const float* __restrict__ mw = nullptr,
-                                                        int mhkv = 1, GfQkv qk = GfQkv{}) {
-    static_assert(MODE != 3 || (LN && NTW == 1 && !HALF && XR == 2), "qkv RoPE epilogue: the B = 1 in_proj");
-    static_assert(!HALF || NTW == 1, "HALF is one half tile");
-    static_assert(!LN || KS * NW * 32 == 2048, "LN prologue: K = 2048");
-    static_assert(!MRG || (!LN && NW == 8 && KS * NW * 32 == 2048), "merge prologue: K = 2048, 8 waves");
-    static_assert(NTW <= NW, "one finishing wave per tile");
-    constexpr bool XC = XR == 2 && !LN && !MRG;          // activation copied to LDS (k_gemv_f)
-    constexpr bool XS = LN || MRG || XC;                             // activation from LDS
-    constexpr int XSTR = XC ? NW * KS * 32 + 8 : GF_XS;              // LDS image row stride (bf16)
-    constexpr int XCN = XC ? KS * 32 * 2 / 512 : 1;                  // XC: 16-B loads per lane (2 rows)
-    static_assert(!XC || (KS * 32 * 2) % 512 == 0, "XC: whole 512-element load rounds per wave");
-    constexpr int KPL = HALF ? 4 : 2;                                // k-steps per weight load
-    constexpr int NL = KS / KPL;                                     // weight loads per wave and tile
-    static_assert(NL * KPL == KS && PF <= NL, "whole loads of paired k-steps");
-    constexpr int LSTR = HALF ? 2048 : 1024;                         // bytes between a lane's loads
-    constexpr int MR = (XR + NW - 1) / NW;                           // LN rows per wave
-    static_assert(!MRG || XR == 2, "merge prologue: M <= 2");
-    __shared__ __attribute__((aligned(16))) uint4 xs[XS ? XR * XSTR / 8 : 1];
-    __shared__ __attribute__((aligned(16))) f32x4 red[NW][NTW][64];
-
-    const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int ln = lane & 15, lg = lane >> 4;
-    const int nt0 = HALF ? (blockIdx.x >> 1) : blockIdx.x * NTW;    // first 16-column tile
-    const int half = HALF ? (blockIdx.x & 1) : 0;
-    const bool wl = !HALF || ((ln >> 3) == half);                   // this lane's column is ours
-    const int ntiles = (N + 63) / 64 * 4;                           // packed rows padded to 64
-    const int kbeg = w * (K / NW);
-    const int mrow = min(ln, M - 1);
-
-    // prologue / epilogue loads first, as in k_gemv_f; the lane's scale byte with them (the column whose
-    // bytes the lane loads: its own, or in the other half of a half tile its neighbour's)
-    uint32_t scb[NTW];
-#pragma unroll
-    for (int tt = 0; tt < NTW; ++tt) scb[tt] = wsc[min(nt0 + tt, ntiles - 1) * 16 + (wl ? ln : (ln ^ 8))];
-    constexpr int NJ = LN ? 4 : 1;                                   // 16-B chunks per lane per row
-    uint4 xv[LN ? MR : 1][NJ] = {}, wv[NJ] = {}, bv[NJ] = {};
-    if constexpr (LN) if (!(XR == 2 && MR == 1) || w < M) {
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            wv[j] = *reinterpret_cast<const uint4*>(lnw + lane * 8 + j * 512);
-            bv[j] = *reinterpret_cast<const uint4*>(lnb + lane * 8 + j * 512);
-        }
-#pragma unroll
-        for (int rr = 0; rr < MR; ++rr)
-#pragma unroll
-            for (int j = 0; j < NJ; ++j)
-                xv[rr][j] = *reinterpret_cast<const uint4*>(A + (size_t)min(w + NW * rr, M - 1) * lda + lane * 8 + j * 512);
-    }
-    uint4 xc[XCN];
-    if constexpr (XC) {
-#pragma unroll
-        for (int j = 0; j < XCN; ++j) {
-            const int e = j * 512 + lane * 8, row = e / (KS * 32), col = e % (KS * 32);
-            xc[j] = *reinterpret_cast<const uint4*>(A + (size_t)min(row, M - 1) * lda + kbeg + col);
-        }
-    }
-    constexpr int NS = MRG ? MRG : 1;
-    float mm[MRG ? 2 : 1][NS], ml[MRG ? 2 : 1][NS];
-    float4 mo[MRG ? 2 : 1][NS];
-    if constexpr (MRG) {
-        const int G = (K >> 7) / mhkv;
-        const int k = kbeg + 4 * lane;
-        const int h = k >> 7, d = k & 127, g = h / G, j = h - g * G;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int m = min(i, M - 1);
-            const float* base = mw + ((size_t)m * mhkv + g) * MRG * GF_AT_STR;
-#pragma unroll
-            for (int sp = 0; sp < NS; ++sp) {
-                mm[i][sp] = base[sp * GF_AT_STR + j];
-                ml[i][sp] = base[sp * GF_AT_STR + GF_AT_G + j];
-                mo[i][sp] = *reinterpret_cast<const float4*>(base + sp * GF_AT_STR + 2 * GF_AT_G + j * 128 + d);
-            }
-        }
-    }
-    int posv = 0;
-    float2 rcs = make_float2(0.f, 0.f);
-    bf16_t rv[4] = {0, 0, 0, 0};                                     // residual x of the epilogue
-    const int t = w;                                                 // wave w finishes tile w
-    const int n_out = (nt0 + t) * 16 + ln;
-    if constexpr (MODE == 2) {
-        if (t < NTW && wl && n_out < N) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) rv[i] = Cb[(size_t)min(lg * 4 + i, M - 1) * N + n_out];
-        }
-    }
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-
-    const int lsrc = wl ? lane * 16 : 1024 + (lane ^ 8) * 16;       // HALF: the next pair for the other half
-    const uint8_t* wp[NTW];
-#pragma unroll
-    for (int tt = 0; tt < NTW; ++tt)
-        wp[tt] = W + ((size_t)min(nt0 + tt, ntiles - 1) * (K >> 6) + (kbeg >> 6)) * 1024 + lsrc;
-    const bf16_t* ap = A + (size_t)mrow * lda + kbeg + lg * 8;
-    constexpr int U = PF + 1;
-    uint4 wr[U][NTW], ar[U][KPL];
-    auto issue = [&](int ls, int slot) {
-#pragma unroll
-        for (int tt = 0; tt < NTW; ++tt) wr[slot][tt] = ldg_w8(wp[tt] + ls * LSTR);
-        if constexpr (!XS) {
-#pragma unroll
-            for (int q = 0; q < KPL; ++q) ar[slot][q] = *reinterpret_cast<const uint4*>(ap + (ls * KPL + q) * 32);
-        }
-    };
-#pragma unroll
-    for (int p = 0; p < PF; ++p)
-        if (p < NL) issue(p, p);
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-    // the skip word (mode 3: and the position word), behind the prologue loads and the weight prefetch
-    int skv;
-    if constexpr (MODE == 3) {
-        ld_words_here(skip, qk.pos, skv, posv);
-        posv = min(max(posv, 0), qk.Smax - 1);
-        const int nq = (qk.H + 2 * qk.Hkv) * 128;      // (N) columns [0, H*128) q, then k, then v
-        const int ncol = min((nt0 + w) * 16 + ln, nq - 1);
-        rcs = *reinterpret_cast<const float2*>(qk.freqs + (size_t)posv * 128 + 2 * ((ncol & 127) >> 1));
-    } else {
-        skv = ld_word_here(skip);
-    }
-    if (skv) {
-#pragma unroll
-        for (int p = 0; p < PF; ++p)
-            if (p < NL) {
-#pragma unroll
-                for (int tt = 0; tt < NTW; ++tt) keep_live(wr[p][tt]);
-            }
-#pragma unroll
-        for (int tt = 0; tt < NTW; ++tt) asm volatile("" ::"v"(scb[tt]));
-        if constexpr (LN) {
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) {
-                keep_live(wv[j]);
-                keep_live(bv[j]);
-#pragma unroll
-                for (int rr = 0; rr < MR; ++rr) keep_live(xv[rr][j]);
-            }
-        }
-        if constexpr (MRG) {
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int sp = 0; sp < NS; ++sp) {
-                    asm volatile("" ::"v"(mm[i][sp]), "v"(ml[i][sp]));
-                    keep_live(mo[i][sp]);
-                }
-        }
-        if constexpr (XC) {
-#pragma unroll
-            for (int j = 0; j < XCN; ++j) keep_live(xc[j]);
-        }
-        if constexpr (MODE == 3) asm volatile("" ::"v"(rcs.x), "v"(rcs.y));
-        if constexpr (MODE == 2) asm volatile("" ::"v"((int)rv[0]), "v"((int)rv[1]), "v"((int)rv[2]), "v"((int)rv[3]));
-        return;
-    }
-
-    if constexpr (LN) {
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            opaque(wv[j]);
-            opaque(bv[j]);
-#pragma unroll
-            for (int rr = 0; rr < MR; ++rr) opaque(xv[rr][j]);
-        }
-        // nn.LayerNorm of each row by one wave: k_gemv_f's arithmetic
-        bf16_t* xsb = reinterpret_cast<bf16_t*>(xs);
-#pragma unroll
-        for (int rr = 0; rr < MR; ++rr) {
-            const int m = w + NW * rr;
-            if (m >= M) break;
-            float xf[NJ * 8];
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) unpack8(xv[rr][j], xf + 8 * j);
-            float s = 0.f;
-#pragma unroll
-            for (int e = 0; e < NJ * 8; ++e) s += xf[e];
-            const float mean = wave_sum_dpp(s) / (float)K;
-            float v = 0.f;
-#pragma unroll
-            for (int e = 0; e < NJ * 8; ++e) { const float d = xf[e] - mean; v += d * d; }
-            const float var = wave_sum_dpp(v) / (float)K;
-            const float rstd = 1.0f / sqrtf(var + eps);
-            const float nb = -rstd * mean;
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) {
-                float wf[8], bf[8], o[8];
-                unpack8(wv[j], wf);
-                unpack8(bv[j], bf);
-#pragma unroll
-                for (int e = 0; e < 8; ++e)
-                    o[e] = __fadd_rn(__fmul_rn(__fadd_rn(__fmul_rn(xf[8 * j + e], rstd), nb), wf[e]), bf[e]);
-                *reinterpret_cast<uint4*>(xsb + m * XSTR + lane * 8 + j * 512) = pack8(o);
-            }
-        }
-        __syncthreads();
-    }
-    if constexpr (XC) {
-        // each wave writes (and later reads) only its own K range: no workgroup barrier
-        bf16_t* xsb = reinterpret_cast<bf16_t*>(xs);
-#pragma unroll
-        for (int j = 0; j < XCN; ++j) {
-            opaque(xc[j]);
-            const int e = j * 512 + lane * 8, row = e / (KS * 32), col = e % (KS * 32);
-            *reinterpret_cast<uint4*>(xsb + row * XSTR + kbeg + col) = xc[j];
-        }
-    }
-    if constexpr (MRG) {
-        // k_attn_combine's arithmetic, split by split in order (fp32, no contraction): k_gemv_f's
-        uint2* xsw = reinterpret_cast<uint2*>(xs);
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-#pragma unroll
-            for (int sp = 0; sp < NS; ++sp) {
-                float2 t2 = make_float2(mm[i][sp], ml[i][sp]);
-                asm volatile("" : "+v"(t2.x), "+v"(t2.y), "+v"(mo[i][sp].x), "+v"(mo[i][sp].y), "+v"(mo[i][sp].z),
-                             "+v"(mo[i][sp].w));
-                mm[i][sp] = t2.x;
-                ml[i][sp] = t2.y;
-            }
-            float Mx = -INFINITY;
-#pragma unroll
-            for (int sp = 0; sp < NS; ++sp) Mx = fmaxf(Mx, mm[i][sp]);
-            float L = 0.f, o0 = 0.f, o1 = 0.f, o2 = 0.f, o3 = 0.f;
-#pragma unroll
-            for (int sp = 0; sp < NS; ++sp) {
-                const float c = (mm[i][sp] == -INFINITY) ? 0.f : __expf(mm[i][sp] - Mx);
-                L += ml[i][sp] * c;
-                o0 += mo[i][sp].x * c;
-                o1 += mo[i][sp].y * c;
-                o2 += mo[i][sp].z * c;
-                o3 += mo[i][sp].w * c;
-            }
-            const float inv = 1.0f / L;
-            const int k = kbeg + 4 * lane;
-            if (i < M) xsw[(i * XSTR + k) >> 2] = make_uint2(pack2(o0 * inv, o1 * inv), pack2(o2 * inv, o3 * inv));
-        }
-    }
-
-    float sc[NTW];
-#pragma unroll
-    for (int tt = 0; tt < NTW; ++tt) sc[tt] = __uint_as_float((scb[tt] & 0xffu) << 23);
-    f32x4 acc[NTW];
-#pragma unroll
-    for (int tt = 0; tt < NTW; ++tt) acc[tt] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const bf16_t* xrow = reinterpret_cast<const bf16_t*>(xs) + mrow * XSTR + kbeg + lg * 8;
-#pragma unroll
-    for (int ls = 0; ls < NL; ++ls) {
-        if (ls + PF < NL) issue(ls + PF, (ls + PF) % U);
-        __builtin_amdgcn_sched_barrier(0);
-        uint4 b0[NTW], b1[NTW];                                      // k-steps 2 pair, 2 pair + 1 of the lane's load
-#pragma unroll
-        for (int tt = 0; tt < NTW; ++tt) {
-            const uint4 raw = wr[ls % U][tt];
-            b0[tt] = w8_cvt8(raw.x, raw.y, sc[tt]);
-            b1[tt] = w8_cvt8(raw.z, raw.w, sc[tt]);
-        }
-#pragma unroll
-        for (int q = 0; q < KPL; ++q) {
-            uint4 a;
-            if constexpr (XS) a = *reinterpret_cast<const uint4*>(xrow + (ls * KPL + q) * 32);
-            else a = ar[ls % U][q];
-#pragma unroll
-            for (int tt = 0; tt < NTW; ++tt) {
-                const uint4 own = (q & 1) ? b1[tt] : b0[tt];
-                const uint4 b = q < 2 ? own : row_ror4<8>(own);
-                acc[tt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_frag(a), as_frag(b), acc[tt], 0, 0, 0);
-            }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    }
-#pragma unroll
-    for (int tt = 0; tt < NTW; ++tt) red[w][tt][lane] = acc[tt];
-    __syncthreads();
-    if (t >= NTW) return;
-    f32x4 sum = red[0][t][lane];
-#pragma unroll
-    for (int q = 1; q < NW; ++q) {
-        const f32x4 o = red[q][t][lane];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) sum[i] = sum[i] + o[i];
-    }
-    if (MODE == 1) {
-        const int F = N / 2;
-        const int f = (nt0 + t) * 8 + (ln & 7);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const float mine = round_bf(sum[i]);
-            const float other = __shfl_xor(mine, 8, 64);
-            const int m = lg * 4 + i;
-            if (ln < 8 && m < M && f < F) {
-                const float sl = round_bf(other / (1.0f + expf(-other)));
-                Cb[(size_t)m * F + f] = f2bf(mine * sl);
-            }
-        }
-        return;
-    }
-    if constexpr (MODE == 3) {
-        const int Hq = qk.H * 128, Hk = qk.Hkv * 128;
-        const int d = n_out & 127;
-        const bool even = (d & 1) == 0;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const float mine = round_bf(sum[i]);
-            const float other = __shfl_xor(mine, 1, 64);      // the pair's other dim (lane ln ^ 1)
-            const int m = lg * 4 + i;
-            if (m >= M || n_out >= N) continue;
-            const float a = even ? mine : other, b = even ? other : mine;
-            const float rot = even ? __fsub_rn(__fmul_rn(a, rcs.x), __fmul_rn(b, rcs.y))
-                                   : __fadd_rn(__fmul_rn(b, rcs.x), __fmul_rn(a, rcs.y));
-            if (n_out < Hq) {
-                Cb[(size_t)m * Hq + n_out] = f2bf(rot);
-            } else if (n_out < Hq + Hk) {
-                const int g = (n_out - Hq) >> 7;
-                qk.kc[((size_t)m * qk.Hkv + g) * qk.Smax * 128 + k_off(posv, d >> 3) + (d & 7)] = f2bf(rot);
-            } else {
-                const int g = (n_out - Hq - Hk) >> 7;
-                qk.vt[((size_t)m * qk.Hkv + g) * qk.Smax * 128 + v_off(posv, d)] = f2bf(mine);
-            }
-        }
-        return;
-    }
-    if (!wl || n_out >= N) return;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int m = lg * 4 + i;
-        if (m >= M) continue;
-        if (MODE == 0) Cf[(size_t)m * N + n_out] = sum[i];
-        else Cb[(size_t)m * N + n_out] = f2bf(bf2f(rv[i]) + round_bf(sum[i]));
-    }
-}
-
-// The form of an FP8 launch: the bf16 form of the same shape (tiles per workgroup, waves, k-steps per
-// wave: the arithmetic), with the prefetch depth counted in this kernel's loads of 2 (HALF: 4) k-steps
-constexpr GfForm gf8_form(int lay, bool ln, int ksw, int xr) {
-    GfForm f = gf_form(lay, ln, ksw, xr);
-    const int nl = f.ks / (f.half ? 4 : 2);
-    f.pf = nl < ZK_GF_PF ? nl : ZK_GF_PF;
-    return f;
-}
 
 // nn.Linear bf16 [N][K] -> the packed e4m3fn image and the scale bytes [Npad] (zonos_amd/wlayout.py), one
 // workgroup per padded row: the row's amax, its scale exponent, then RNE bytes of w * 2^-e in image order
@@ -1780,8 +1551,8 @@ __global__ __launch_bounds__(256) void k_pack_w8(const bf16_t* __restrict__ w, i
             for (int e = 0; e < 8; ++e) amax = fmaxf(amax, fabsf(f[e]));
         }
     amax = block_max<256>(amax, red);
-    const int ex = w8_scale_exp(amax);
-    const float inv = __uint_as_float((uint32_t)(127 - ex) << 23);    // 2^-ex, ex in [-126, 126] for finite bf16
+    const int ex = kv_scale_exp(amax);                                // (common.h: the FP8 KV cache's rule)
+    const float inv = kv_pow2(-ex);                                   // ex in [-126, 126] for finite bf16
     if (threadIdx.x == 0) scales[n] = real ? (uint8_t)(ex + 127) : (uint8_t)127;
     for (int c = threadIdx.x; c < K / 8; c += 256) {
         const int k = c * 8;
@@ -1810,80 +1581,6 @@ extern "C" int zk_pack_weights_e4m3(const void* w, int N, int K, void* out, void
     hipLaunchKernelGGL(k_pack_w8, dim3(Npad), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)w, N, K, (uint8_t*)out,
                        (uint8_t*)scales);
     ZK_CHECK_LAUNCH("zk_pack_weights_e4m3");
-    return 0;
-}
-
-extern "C" int zk_gemv_fused_w8(const void* A, long lda, const void* W8, const void* w_scale, int M, int N, int K,
-                                int mode, const void* ln_w, const void* ln_b, float eps, float* Cf, void* Cb,
-                                const int32_t* skip_flag, void* stream) {
-    ZK_REQUIRE(M >= 1 && M <= 16 && N > 0, "zk_gemv_fused_w8: M=%d (1..16) N=%d", M, N);
-    ZK_REQUIRE(K == 2048 || K == 4096 || K == 8192, "zk_gemv_fused_w8: K=%d (2048, 4096 or 8192)", K);
-    ZK_REQUIRE(lda >= K && lda % 8 == 0 && lda <= (1L << 30), "zk_gemv_fused_w8: lda=%ld", lda);
-    ZK_REQUIRE(mode >= 0 && mode <= 2, "zk_gemv_fused_w8: mode %d", mode);
-    ZK_REQUIRE(mode != 1 || N % 16 == 0, "zk_gemv_fused_w8: SwiGLU needs N %% 16 == 0");
-    ZK_REQUIRE((ln_w == nullptr) == (ln_b == nullptr), "zk_gemv_fused_w8: LN needs both w and b");
-    ZK_REQUIRE(ln_w == nullptr || K == 2048, "zk_gemv_fused_w8: LN prologue needs K = 2048 (K=%d)", K);
-    ZK_REQUIRE(mode == 0 ? Cf != nullptr : Cb != nullptr, "zk_gemv_fused_w8: missing output");
-    ZK_REQUIRE(W8 != nullptr && w_scale != nullptr, "zk_gemv_fused_w8: missing weight image or scales");
-    const GemvPlan p = gemv_plan(M, N, K, mode, ln_w != nullptr);
-    bool launched = false;
-    pick([&](auto mode_, auto ln, auto lay, auto ksw, auto xr) {
-        if constexpr (gf_has(mode_(), ln() != 0, lay(), ksw())) {
-            constexpr GfForm F = gf8_form(lay(), ln() != 0, ksw(), xr());
-            hipLaunchKernelGGL((k_gemv_w8<mode_(), ln() != 0, F.ntw, F.half, F.nw, F.ks, F.pf, 0, xr()>), dim3(p.grid),
-                               dim3(p.block), 0, (hipStream_t)stream, (const bf16_t*)A, (const uint8_t*)W8,
-                               (const uint8_t*)w_scale, (int)lda, M, N, K, (const bf16_t*)ln_w, (const bf16_t*)ln_b, eps,
-                               Cf, (bf16_t*)Cb, skip_flag, nullptr, 1);
-            launched = true;
-        }
-    }, mode, Ints<0, 1, 2>{}, ln_w != nullptr, Ints<0, 1>{}, p.lay, Ints<0, 1, 2>{}, p.ksw, Ints<64, 128, 256>{}, p.xr,
-         Ints<2, 16>{});
-    ZK_REQUIRE(launched, "zk_gemv_fused_w8: no kernel for K=%d", K);
-    ZK_CHECK_LAUNCH("zk_gemv_fused_w8");
-    return 0;
-}
-
-extern "C" int zk_gemv_qkv_rope_w8(const void* x, const void* W8, const void* w_scale, int M, int H, int Hkv, int hd,
-                                   const void* ln_w, const void* ln_b, float eps, void* q_out, void* k_cache,
-                                   void* vt_cache, int Smax, const int32_t* pos_dev, const float* freqs,
-                                   const int32_t* skip_flag, void* stream) {
-    ZK_REQUIRE(M >= 1 && M <= 2, "zk_gemv_qkv_rope_w8: M=%d (1..2)", M);
-    ZK_REQUIRE(hd == 128 && H % Hkv == 0 && H / Hkv <= AT_G, "zk_gemv_qkv_rope_w8: H=%d Hkv=%d hd=%d", H, Hkv, hd);
-    const int K = H * hd, N = (H + 2 * Hkv) * hd;
-    ZK_REQUIRE(K == 2048, "zk_gemv_qkv_rope_w8: d_model %d (2048 only: the LayerNorm prologue)", K);
-    ZK_REQUIRE(x && W8 && w_scale && ln_w && ln_b && q_out && k_cache && vt_cache && pos_dev && freqs,
-               "zk_gemv_qkv_rope_w8: null argument");
-    ZK_REQUIRE(Smax > 0 && Smax % 32 == 0, "zk_gemv_qkv_rope_w8: Smax=%d", Smax);
-    const GfQkv qk{(bf16_t*)k_cache, (bf16_t*)vt_cache, pos_dev, freqs, H, Hkv, Smax};
-    const GemvPlan p = gemv_plan(M, N, K, 3, true);
-    ZK_REQUIRE(p.lay == 1 && p.xr == 2, "zk_gemv_qkv_rope_w8: N=%d is not a one-tile GEMV", N);
-    constexpr GfForm F = gf8_form(1, true, 64, 2);
-    hipLaunchKernelGGL((k_gemv_w8<3, true, F.ntw, F.half, F.nw, F.ks, F.pf, 0, 2>), dim3(p.grid), dim3(p.block), 0,
-                       (hipStream_t)stream, (const bf16_t*)x, (const uint8_t*)W8, (const uint8_t*)w_scale, K, M, N, K,
-                       (const bf16_t*)ln_w, (const bf16_t*)ln_b, eps, nullptr, (bf16_t*)q_out, skip_flag, nullptr, 1,
-                       qk);
-    ZK_CHECK_LAUNCH("zk_gemv_qkv_rope_w8");
-    return 0;
-}
-
-extern "C" int zk_gemv_attn_out_w8(const float* work, int nsplit, int Hkv, const void* W8, const void* w_scale, int M,
-                                   int N, int K, void* x, const int32_t* skip_flag, void* stream) {
-    ZK_REQUIRE(M >= 1 && M <= 2, "zk_gemv_attn_out_w8: M=%d (1..2)", M);
-    ZK_REQUIRE(K == 2048 && N > 0 && N % 16 == 0, "zk_gemv_attn_out_w8: K=%d (2048) N=%d", K, N);
-    ZK_REQUIRE(Hkv >= 1 && (K / 128) % Hkv == 0 && (K / 128) / Hkv <= GF_AT_G, "zk_gemv_attn_out_w8: Hkv=%d", Hkv);
-    ZK_REQUIRE(work != nullptr && x != nullptr && W8 != nullptr && w_scale != nullptr,
-               "zk_gemv_attn_out_w8: null buffer");
-    // zk_gemv_attn_out's form (half tiles, 8 K-range waves of 8 k-steps): two loads of 4 k-steps per wave
-    constexpr GfForm F{1, true, 8, 8, 2};
-    static_assert(ZK_GF_NWH != 8 || ZK_GF_PF < 2 || F == gf8_form(0, false, 64, 2), "zk_gemv_attn_out_w8's layout");
-    const bool listed = pick([&](auto ns) {
-        hipLaunchKernelGGL((k_gemv_w8<2, false, F.ntw, F.half, F.nw, F.ks, F.pf, ns(), 2>),
-                           dim3(gf_grid(0, (N + 15) / 16)), dim3(64 * F.nw), 0, (hipStream_t)stream,
-                           reinterpret_cast<const bf16_t*>(work), (const uint8_t*)W8, (const uint8_t*)w_scale, K, M, N, K,
-                           nullptr, nullptr, 0.f, nullptr, (bf16_t*)x, skip_flag, work, Hkv);
-    }, nsplit, Ints<2, 4, 8, 16>{});
-    ZK_REQUIRE(listed, "zk_gemv_attn_out_w8: nsplit=%d (2, 4, 8 or 16)", nsplit);
-    ZK_CHECK_LAUNCH("zk_gemv_attn_out_w8");
     return 0;
 }
 

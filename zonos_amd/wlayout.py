@@ -1,5 +1,5 @@
-"""Host-side view of the FP8 (e4m3fn) weight format of the small-batch decode GEMVs (gemm.hip k_gemv_w8;
-generate(weight_dtype="fp8")).
+"""Host-side view of the FP8 (e4m3fn) weight format of the small-batch decode GEMVs (gemm.hip: the
+WsE4m3 weight stream of gemv_body, entry kernel k_gemv_w8; generate(weight_dtype="fp8")).
 
 Format: a weight W[N][K] (nn.Linear order, bf16) becomes OCP e4m3fn bytes with one power-of-two scale per
 output row n, stored as its biased exponent byte b (E8M0, scale 2^(b-127)). The scale rule is
