@@ -90,6 +90,17 @@ def test_mamba_step_kernel_vs_oracle(c):
     out = F.linear(ym.cpu(), W[p + "out_proj.weight"])
     err = (out.float() - ref_out[:, 0].float()).abs()
     assert err.max() < 0.05 * ref_out.float().abs().max() and err.mean() < 5e-3, (err.max(), err.mean())
+    # the derived elementwise bound (tests/mamba_probe.py) on the state and on yz before out_proj
+    from . import mamba_probe as mp
+    P = mp.Params(conv_w=cw.cpu().numpy(), conv_b=cb.cpu().numpy(), A=A.cpu().numpy(), dt_bias=dtb.cpu().numpy(),
+                  D=Dv.cpu().numpy(), norm_w=nw.cpu().numpy())
+    ref = mp.reference(parts.numpy()[:, :, None, :], P, conv0=conv0.float().numpy(), ssm0=ssm0.float().numpy(),
+                       round_at=mp.round_points(1, 0))
+    r_ssm = mp.ratio(ssm.cpu().float().numpy(), ref.ssm, ref.e_ssm)
+    r_yz = mp.ratio(yz.cpu().numpy(), ref.yz[:, 0], ref.e_yz[:, 0])
+    r_out = mp.ratio(ym.cpu().float().numpy(), ref.out[:, 0], ref.e_out[:, 0])
+    print(f"derived bound: ssm {r_ssm:.3f}, yz {r_yz:.3f}, norm {r_out:.3f}")
+    assert r_ssm <= 1 and r_yz <= 1 and r_out <= 1, (r_ssm, r_yz, r_out)
 
 
 def test_hybrid_generate_teacher_forced_logits():
