@@ -338,6 +338,40 @@ int zk_sample_heads(const float* part, int nsplit, const zk_gen_state* st, const
  * first frame (model.py:310-319). */
 int zk_eos_step(const zk_gen_state* st, int prefill, int prefix_len, void* stream);
 
+/* ------------------------------------------------------------------ request batches
+ * A batch of independent requests: utterance b samples with its own parameters and its own noise key and
+ * runs the EOS protocol on its own, so its codes are what Zonos.generate (model.py:224-457) returns for
+ * it at batch size 1, whatever else shares the batch. The reference has one sampling_params / cfg_scale
+ * for the whole batch (model.py:224-247) and redraws EVERY row when any row emits its first EOS
+ * (model.py:380-393), which couples the rows; zk_sample_heads / zk_eos_step keep that protocol. */
+typedef struct zk_row_params {
+    zk_sampling_params sp;   /* this utterance's, cfg_scale and force_full_length included */
+    uint64_t seed;           /* keyed-noise seed */
+    int32_t  key;            /* row index the noise is keyed by (in place of row_base + b) */
+    int32_t  reserved;       /* 0 */
+} zk_row_params;
+
+/* zk_sample_heads with per-utterance parameters (replaces sample_from_logits' batch-wide arguments,
+ * model.py:365,388, and the batch-wide cfg_scale of model.py:112-114): rows = device zk_row_params
+ * [st->B]; workgroup (b, k) reads rows[b] with its other up-front loads. The noise is the keyed stream
+ * of (rows[b].seed, step, draw, rows[b].key, codebook, token); st->seed / st->row_base are not read and
+ * st->noise_mode must be 0 (torch's stream is one call per batch). draw 1 (model.py:386-393) runs for
+ * row b only when row b itself has a new EOS (tok0[b*K] == EOS and !eos_mode[b]); every other row's
+ * workgroups return. Per row this is zk_sample_heads at B = 1 with that row's parameters, bit for bit.
+ * Window contract: 1 <= rows[b].sp.rp_window <= 512 for every b is the CALLER's to keep -- the
+ * parameters are in device memory, which this entry cannot read; the kernel clamps the window to 512
+ * columns, so a violation stays in bounds but does not match the reference. Errors before any launch:
+ * a NULL argument (rows included), st->noise_mode != 0, V out of range. */
+int zk_sample_heads_rows(const float* part, int nsplit, const zk_gen_state* st, const zk_row_params* rows,
+                         int prefill, int draw, float* dbg_logits, void* stream);   /* rows: device [st->B] */
+/* zk_eos_step for a request batch (model.py:376-424 per row): row b takes the draw-1 tokens iff row b
+ * itself had the new EOS (model.py:380-393 at batch size 1), else the draw-0 tokens; hold-off,
+ * remaining = min(remaining, 9), the MASK / EOS staircase, the counters and the done word are
+ * zk_eos_step's. Per-row budgets are the host's: remaining[b] starts at n_b + 8 and Ld fits the largest
+ * n_b; a row whose budget is spent is still stepped until the done word (its cells past the budget hold
+ * MASK from the host's delay pattern, so it writes nothing there; the kernel does not freeze it). */
+int zk_eos_step_rows(const zk_gen_state* st, int prefill, int prefix_len, void* stream);
+
 /* ------------------------------------------------------------------ one decode step
  * The whole autoregressive step of Zonos.generate (model.py:322-424: _decode_one_token's
  * embed -> 26 blocks -> norm_f -> 9 heads -> CFG, then the sampler, the EOS protocol and the
@@ -411,6 +445,11 @@ typedef struct zk_step_desc {
     void* pre_vt;
     int32_t pre_smax;
     int32_t w_fp8;                 /* 0: bf16 weights; 1: FP8 (e4m3fn) layer weights, small must be 1 (above) */
+    /* NULL (a zeroed field): the batch-wide sampler and EOS protocol above. Non-NULL, device
+     * zk_row_params [B]: a request batch -- zk_decode_step and zk_prefill enqueue zk_sample_heads_rows /
+     * zk_eos_step_rows in place of zk_sample_heads / zk_eos_step (sp, st.seed and st.row_base are then
+     * not read); with st.noise_mode == 1 both fail before any launch. */
+    const zk_row_params* rows;
 } zk_step_desc;
 
 int zk_decode_step(const zk_step_desc* d, void* stream);
@@ -495,6 +534,7 @@ typedef struct zk_hybrid_desc {
     zk_gen_state st;
     zk_sampling_params sp;
     void* xf;                      /* residual rows fp32 [rows][D] (norm_flags bit 2; else unused) */
+    const zk_row_params* rows;     /* NULL, or a request batch: as zk_step_desc.rows, for the two entries below */
 } zk_hybrid_desc;
 
 int zk_hybrid_decode_step(const zk_hybrid_desc* d, void* stream);

@@ -6,6 +6,7 @@ Callers written against the reference -- sample.py:9-11, zonos_batch_cli.py:13-1
 package like the reference's (no __init__.py)."""
 from zonos_amd.engine import AudioStream, StreamChunk  # noqa: F401  (what Zonos.stream() returns and yields)
 from zonos_amd.model import Zonos  # noqa: F401
+from zonos_amd.requests import Request  # noqa: F401  (one utterance of Zonos.generate_requests())
 
 from .backbone import BACKBONES
 

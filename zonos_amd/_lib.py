@@ -36,6 +36,11 @@ class GenState(C.Structure):
                 ("noise_stride", C.c_int32), ("noise_incr", C.c_int32)]
 
 
+class RowParams(C.Structure):
+    """zk_row_params: one utterance of a request batch (its sampling parameters, keyed-noise seed and key)."""
+    _fields_ = [("sp", SamplingParams), ("seed", U64), ("key", C.c_int32), ("reserved", C.c_int32)]
+
+
 class StepLayer(C.Structure):
     _fields_ = [("ln1_w", P), ("ln1_b", P), ("wqkv", P), ("wo", P), ("ln2_w", P), ("ln2_b", P), ("fc1", P),
                 ("fc2", P), ("k_cache", P), ("vt_cache", P), ("k_scale", P), ("v_scale", P),
@@ -50,7 +55,7 @@ class StepDesc(C.Structure):
               [("eps", F), ("kv_fp8", C.c_int32), ("layers", P), ("emb", P), ("heads", P), ("lnf_w", P), ("lnf_b", P),
                ("freqs", P), ("x", P), ("xn", P), ("y", P), ("h", P), ("part", P), ("attn_work", P), ("attn_cnt", P),
                ("dbg", P), ("st", GenState), ("sp", SamplingParams), ("pre_k", P), ("pre_vt", P),
-               ("pre_smax", C.c_int32), ("w_fp8", C.c_int32)]
+               ("pre_smax", C.c_int32), ("w_fp8", C.c_int32), ("rows", P)]
 
 
 class HybridLayer(C.Structure):
@@ -67,7 +72,7 @@ class HybridDesc(C.Structure):
                                          "norm_flags")] + \
               [("eps", F), ("gate_eps", F), ("layers", P), ("emb", P), ("heads", P), ("lnf_w", P), ("lnf_b", P),
                ("freqs", P), ("x", P), ("xn", P), ("y", P), ("h", P), ("part", P), ("attn_work", P), ("yz", P),
-               ("ym", P), ("xc", P), ("dbg", P), ("st", GenState), ("sp", SamplingParams), ("xf", P)]
+               ("ym", P), ("xc", P), ("dbg", P), ("st", GenState), ("sp", SamplingParams), ("xf", P), ("rows", P)]
 
 
 class DacResUnit(C.Structure):
@@ -153,6 +158,8 @@ _SIGS = {
     "zk_attn_prefill": [P, P, P, I, I, I, I, I, I, P, P],
     "zk_sample_heads": [P, I, C.POINTER(GenState), C.POINTER(SamplingParams), I, I, P, P],
     "zk_eos_step": [C.POINTER(GenState), I, I, P],
+    "zk_sample_heads_rows": [P, I, C.POINTER(GenState), P, I, I, P, P],
+    "zk_eos_step_rows": [C.POINTER(GenState), I, I, P],
     "zk_graph_begin": [P],
     "zk_graph_end": [P, C.POINTER(P)],
     "zk_graph_launch": [P, I, P],

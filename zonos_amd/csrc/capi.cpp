@@ -19,6 +19,9 @@
 #pragma weak zk_gemv_fused_w8
 #pragma weak zk_gemv_qkv_rope_w8
 #pragma weak zk_gemv_attn_out_w8
+// The request-batch sampler entries (sampler.hip), weak in the same way; rows_ok() refuses rows without them.
+#pragma weak zk_sample_heads_rows
+#pragma weak zk_eos_step_rows
 
 static thread_local char g_err[1024] = "";
 
@@ -37,7 +40,7 @@ extern "C" int zk_version(void) { return 2; }
 // layout without a GPU: which = 0 zk_sampling_params, 1 zk_gen_state, 4 ZkCondSeg, 5 ZkCondPlan,
 // 6 zk_step_layer, 7 zk_step_desc, 8 zk_dac_desc; 12-25 sizes / field offsets (see the cases);
 // 26-30 zk_spk_block / zk_spk_desc; 31-32 the FP8-weight fields of zk_step_desc / zk_step_layer;
-// 33-34 zk_stream_desc.
+// 33-34 zk_stream_desc; 35-39 zk_row_params and the rows field of zk_step_desc / zk_hybrid_desc.
 extern "C" long zk_abi_size(int which) {
     switch (which) {
         case 0: return (long)sizeof(zk_sampling_params);
@@ -70,6 +73,11 @@ extern "C" long zk_abi_size(int which) {
         case 32: return (long)offsetof(zk_step_layer, wqkv8);
         case 33: return (long)sizeof(zk_stream_desc);
         case 34: return (long)offsetof(zk_stream_desc, B);
+        case 35: return (long)sizeof(zk_row_params);
+        case 36: return (long)offsetof(zk_row_params, seed);
+        case 37: return (long)offsetof(zk_row_params, key);
+        case 38: return (long)offsetof(zk_step_desc, rows);
+        case 39: return (long)offsetof(zk_hybrid_desc, rows);
         default: return -1;
     }
 }
@@ -199,13 +207,37 @@ int prefill_epilogue(const Desc* d, int S, int P, void* stream) {
     const int R = 2 * d->B, D = d->d_model;
     ZK_STEP(zk_gemm_bf16(static_cast<const char*>(d->xn) + (size_t)(S - 1) * D * 2, (long)S * D, d->heads, R,
                          d->st.K * d->st.V, D, d->split_heads, 0, d->part, nullptr, nullptr, stream));
+    if (d->rows != nullptr) {   // a request batch: per-utterance parameters
+        ZK_STEP(zk_sample_heads_rows(d->part, d->split_heads, &d->st, d->rows, 1, 0, d->dbg, stream));
+        return zk_eos_step_rows(&d->st, 1, P + 1, stream);
+    }
     ZK_STEP(zk_sample_heads(d->part, d->split_heads, &d->st, &d->sp, 1, 0, d->dbg, stream));
     return zk_eos_step(&d->st, 1, P + 1, stream);
+}
+
+// A request batch (rows != NULL) samples from the keyed noise only; checked before the first launch
+template <class Desc>
+int rows_ok(const char* who, const Desc* d) {
+    if (d->rows != nullptr && (&zk_sample_heads_rows == nullptr || &zk_eos_step_rows == nullptr)) {
+        zk_set_error("%s: this build has no request-batch sampler kernels", who);
+        return -1;
+    }
+    if (d->rows != nullptr && d->st.noise_mode != 0) {
+        zk_set_error("%s: rows (a request batch) takes the keyed noise only, st.noise_mode = %d (torch's stream is "
+                     "one call per batch)", who, d->st.noise_mode);
+        return -1;
+    }
+    return 0;
 }
 
 // Decode tail: both sampler draws over the nsp logit slabs in part, then the EOS protocol
 template <class Desc>
 int decode_tail(const Desc* d, int nsp, void* stream) {
+    if (d->rows != nullptr) {   // a request batch: per-utterance parameters, rows independent
+        ZK_STEP(zk_sample_heads_rows(d->part, nsp, &d->st, d->rows, 0, 0, d->dbg, stream));
+        ZK_STEP(zk_sample_heads_rows(d->part, nsp, &d->st, d->rows, 0, 1, nullptr, stream));
+        return zk_eos_step_rows(&d->st, 0, 0, stream);
+    }
     ZK_STEP(zk_sample_heads(d->part, nsp, &d->st, &d->sp, 0, 0, d->dbg, stream));
     ZK_STEP(zk_sample_heads(d->part, nsp, &d->st, &d->sp, 0, 1, nullptr, stream));
     return zk_eos_step(&d->st, 0, 0, stream);
@@ -350,6 +382,7 @@ extern "C" int zk_decode_step(const zk_step_desc* d, void* stream) {
         zk_set_error("zk_decode_step: bad descriptor");
         return -1;
     }
+    ZK_STEP(rows_ok("zk_decode_step", d));
     ZK_STEP(fp8_ok("zk_decode_step", d, false, 0));
     ZK_STEP(w8_ok("zk_decode_step", d));
     const int K = d->st.K, V = d->st.V, B = d->B, R = 2 * B;
@@ -407,6 +440,7 @@ extern "C" int zk_decode_step(const zk_step_desc* d, void* stream) {
 }
 
 extern "C" int zk_prefill(const zk_step_desc* d, const void* cond, int Lc, int P, void* q, void* stream) {
+    if (step_ok(d)) ZK_STEP(rows_ok("zk_prefill", d));
     if (step_ok(d)) ZK_STEP(fp8_ok("zk_prefill", d, true, Lc + P + 1));
     ZK_STEP(prefill_prologue("zk_prefill", step_ok(d), d, cond, Lc, P, q, stream));
     const int R = 2 * d->B, S = Lc + P + 1;
@@ -529,6 +563,7 @@ extern "C" int zk_hybrid_decode_step(const zk_hybrid_desc* d, void* stream) {
         zk_set_error("zk_hybrid_decode_step: bad descriptor");
         return -1;
     }
+    ZK_STEP(rows_ok("zk_hybrid_decode_step", d));
     const int K = d->st.K, V = d->st.V, B = d->B, R = 2 * B, D = d->d_model;
     int32_t* scal = d->st.scal;
     const int32_t* skip = scal + 3;
@@ -543,6 +578,7 @@ extern "C" int zk_hybrid_decode_step(const zk_hybrid_desc* d, void* stream) {
 }
 
 extern "C" int zk_hybrid_prefill(const zk_hybrid_desc* d, const void* cond, int Lc, int P, void* q, void* stream) {
+    if (hybrid_ok(d)) ZK_STEP(rows_ok("zk_hybrid_prefill", d));
     ZK_STEP(prefill_prologue("zk_hybrid_prefill", hybrid_ok(d), d, cond, Lc, P, q, stream));
     const int R = 2 * d->B, S = Lc + P + 1, D = d->d_model;
     if (d->norm_flags & 6) ZK_STEP(hybrid_prenorm(d, R * S, nullptr, stream));

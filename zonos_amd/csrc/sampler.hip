@@ -343,101 +343,39 @@ __global__ __launch_bounds__(NT) void k_sample_logits(const float* logits, int B
     if (threadIdx.x == 0) out[(size_t)b * K + k] = t;
 }
 
-// Engine sampler: CFG-combine the heads GEMM slabs, bias, EOS masks, sample.
+// Engine sampler: CFG-combine the heads GEMM slabs, bias, EOS masks, sample. One body (sampler_heads_body.inc),
+// two entries. k_sample_heads<TN>: the batch-wide parameters by value. k_sample_heads_rows (a request batch,
+// zk_sample_heads_rows): the fourth argument is the device array of per-utterance parameters; utterance b's
+// sampling parameters, CFG scale, seed and noise key come from rows[b], and draw 1 runs for the rows that
+// themselves have a new EOS only. A kernel of its own name, so the batch-wide kernels keep their arguments,
+// their preloaded argument dwords and their code.
+// What the body reads its parameters through: the batch-wide ones, or rows[b]
+ZK_DEV zk_row_params heads_row(const zk_sampling_params&, int) { return zk_row_params{}; }
+ZK_DEV zk_row_params heads_row(const zk_row_params* rows, int b) { return rows[b]; }
+ZK_DEV const zk_sampling_params& heads_sp(const zk_sampling_params& sp, const zk_row_params&) { return sp; }
+ZK_DEV const zk_sampling_params& heads_sp(const zk_row_params*, const zk_row_params& rw) { return rw.sp; }
+
 template <bool TN>
 __global__ __launch_bounds__(NT) void k_sample_heads(const float* part, int nsplit, zk_gen_state st,
-                                                     zk_sampling_params sp, int prefill, int draw,
+                                                     zk_sampling_params spa, int prefill, int draw,
                                                      float* dbg) {
+    constexpr bool ROWS = false;
     __shared__ Smem s;
-    const int B = st.B, K = st.K, V = st.V;
-    const int b = blockIdx.x / K, k = blockIdx.x % K;
-    const int32_t* scal = st.scal;
-    // Every load that does not depend on another one is issued up front (one memory round trip):
-    // the done word, the step scalars, this row's state and the logits; the finished check comes
-    // after them (the loads are in bounds either way).
-    const int done = scal[3];
-    const int offset = scal[0], step = scal[2], nres = scal[4];
-    const float rpb = st.rp[b];
-    const int actb = st.act[b];
-    int new_eos_b = 0;
-    if (draw == 1) {   // EOS resample happens only if some row has a new EOS (model.py:380)
-        int any = 0;   // one row per thread
-        for (int r = threadIdx.x; r < B; r += NT) any |= (st.tok0[r * K] == EOS) && !st.eos_mode[r];
-        if (!__syncthreads_or(any && !done)) return;
-        new_eos_b = (st.tok0[b * K] == EOS) && !st.eos_mode[b];
-    }
-    const size_t N = (size_t)K * V;
-    const size_t slab = (size_t)2 * B * N;
-    const float* pc = part + (size_t)b * N + (size_t)k * V;
-    const float* pu = part + (size_t)(b + B) * N + (size_t)k * V;
-    float x[NPT];
-    if (nsplit == 1) {     // the unsplit heads GEMM (c3, B <= 8): all 2 x NPT loads before the first use
-        float c1[NPT], u1[NPT];
-#pragma unroll
-        for (int i = 0; i < NPT; ++i) {
-            const int v = min(threadIdx.x + NT * i, V - 1);
-            c1[i] = pc[v];
-            u1[i] = pu[v];
-        }
-#pragma unroll
-        for (int i = 0; i < NPT; ++i) {
-            const int v = threadIdx.x + NT * i;
-            float val = -INFINITY;
-            if (v < V) {
-                const float c = round_bf(0.f + c1[i]), u = round_bf(0.f + u1[i]);   // head output bf16 (model.py:111)
-                val = __fadd_rn(u, __fmul_rn(__fsub_rn(c, u), sp.cfg_scale));       // model.py:114
-                if (v >= 1025) val = -INFINITY;                                    // model.py:115
-            }
-            x[i] = val;
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < NPT; ++i) {
-        if (nsplit == 1) break;
-        const int v = threadIdx.x + NT * i;
-        float val = -INFINITY;
-        if (v < V) {
-            float c = 0.f, u = 0.f;
-            for (int sp_ = 0; sp_ < nsplit; ++sp_) { c += pc[sp_ * slab + v]; u += pu[sp_ * slab + v]; }
-            c = round_bf(c); u = round_bf(u);                              // head output bf16 (model.py:111)
-            val = __fadd_rn(u, __fmul_rn(__fsub_rn(c, u), sp.cfg_scale)); // model.py:114
-            if (v >= 1025) val = -INFINITY;                                // model.py:115
-        }
-        x[i] = val;
-    }
-    if (done) return;                                       // generation finished
-    if (dbg != nullptr && draw == 0) {
-        float* d = dbg + ((size_t)b * K + k) * V;
-#pragma unroll
-        for (int i = 0; i < NPT; ++i) { const int v = threadIdx.x + NT * i; if (v < V) d[v] = x[i]; }
-    }
-    // bias + EOS masks for the EOS column only (threads owning v == EOS)
-#pragma unroll
-    for (int i = 0; i < NPT; ++i) {
-        const int v = threadIdx.x + NT * i;
-        if (v == EOS) {
-            if (!prefill) {
-                if (k >= 1) x[i] = -INFINITY;                                  // model.py:323
-                else x[i] = __fadd_rn(x[i], 0.0f - LOG1024F);                  // model.py:324,353
-                if (k == 0 && actb) x[i] = -INFINITY;                          // model.py:360-361
-                if (k == 0 && new_eos_b) x[i] = -INFINITY;                     // model.py:387
-            }
-            if (k == 0 && sp.force_full_length) x[i] = -INFINITY;              // benchmark mode
-        }
-    }
-    // torch noise mode: the reference's sampler calls so far -- the prefill sample, one per earlier
-    // decode step (scal[2] starts at 1) and one per earlier EOS resample (scal[4]) -- each took
-    // noise_incr of the generator's Philox offset (model.py:304,365,388)
-    const long call = prefill ? 0 : (long)step + nres + draw;
-    RowCtx c{b, k, V, prefill ? nullptr : st.delayed + ((size_t)b * K + k) * st.Ld, offset,
-             prefill ? 1.f : rpb, prefill ? 0 : step, draw, st.row_base + b, st.seed,
-             st.noise_offset + (uint64_t)call * (uint64_t)st.noise_incr, st.noise_mode ? st.noise_stride : 0,
-             ((long)(st.row_base + b) * K + k) * V};
-    const int t = sample_row<TN>(x, c, sp, s);
-    if (threadIdx.x == 0) (draw ? st.tok1 : st.tok0)[b * K + k] = t;
+#include "sampler_heads_body.inc"
+}
+
+__global__ __launch_bounds__(NT) void k_sample_heads_rows(const float* part, int nsplit, zk_gen_state st,
+                                                          const zk_row_params* spa, int prefill, int draw,
+                                                          float* dbg) {
+    constexpr bool TN = false, ROWS = true;   // keyed noise only: torch's stream is one call per batch
+    __shared__ Smem s;
+#include "sampler_heads_body.inc"
 }
 
 // EOS protocol, frame write and step counters (model.py:376-424), one workgroup.
+// ROWS (a request batch, zk_eos_step_rows): row b takes the draw-1 tokens iff row b itself had the new EOS
+// -- what the batch-wide protocol does at B = 1; everything else is shared.
+template <bool ROWS>
 __global__ __launch_bounds__(NT) void k_eos_step(zk_gen_state st, int prefill, int prefix_len) {
     __shared__ int s_any, s_max;
     const int B = st.B, K = st.K, Ld = st.Ld;
@@ -459,7 +397,7 @@ __global__ __launch_bounds__(NT) void k_eos_step(zk_gen_state st, int prefill, i
     const int offset = scal[0];
     for (int b = threadIdx.x; b < B; b += NT) {
         const int newe = (st.tok0[b * K] == EOS) && !st.eos_mode[b];
-        const int32_t* tok = (any ? st.tok1 : st.tok0) + b * K;
+        const int32_t* tok = ((ROWS ? newe : any) ? st.tok1 : st.tok0) + b * K;
         if (newe) { st.eos_mode[b] = 1; st.steps_after[b] = 6; }          // model.py:383-384
         int rem = st.remaining[b];
         if (tok[0] == EOS) { rem = min(rem, 9); st.stopping[b] = 1; }      // model.py:399-402
@@ -618,8 +556,33 @@ extern "C" int zk_sample_heads(const float* part, int nsplit, const zk_gen_state
 extern "C" int zk_eos_step(const zk_gen_state* st, int prefill, int prefix_len, void* stream) {
     ZK_REQUIRE(st != nullptr, "zk_eos_step: null state");
     ZK_REQUIRE(st->K <= EOS_MAXK, "zk_eos_step: K=%d codebooks > %d", st->K, EOS_MAXK);
-    hipLaunchKernelGGL(k_eos_step, dim3(1), dim3(NT), 0, (hipStream_t)stream, *st, prefill, prefix_len);
+    hipLaunchKernelGGL(k_eos_step<false>, dim3(1), dim3(NT), 0, (hipStream_t)stream, *st, prefill, prefix_len);
     ZK_CHECK_LAUNCH("zk_eos_step");
+    return 0;
+}
+
+extern "C" int zk_sample_heads_rows(const float* part, int nsplit, const zk_gen_state* st, const zk_row_params* rows,
+                                    int prefill, int draw, float* dbg_logits, void* stream) {
+    ZK_REQUIRE(st && part, "zk_sample_heads_rows: null argument");
+    ZK_REQUIRE(rows != nullptr, "zk_sample_heads_rows: null rows (the device zk_row_params [B] of the request batch)");
+    ZK_REQUIRE(!st->noise_mode, "zk_sample_heads_rows: a request batch takes the keyed noise only (noise_mode %d: "
+               "torch's stream is one call per batch)", st->noise_mode);
+    ZK_REQUIRE(st->V > 0 && st->V <= NT * NPT, "zk_sample_heads_rows: V=%d unsupported", st->V);
+    ZK_REQUIRE(st->B > 0 && st->K > 0 && nsplit >= 1, "zk_sample_heads_rows: B=%d K=%d nsplit=%d", st->B, st->K, nsplit);
+    // the window contract (1 <= rp_window <= MAXW per row) is the caller's: the parameters are device memory
+    hipLaunchKernelGGL(k_sample_heads_rows, dim3(st->B * st->K), dim3(NT), 0, (hipStream_t)stream, part,
+                       nsplit, *st, rows, prefill, draw, dbg_logits);
+    ZK_CHECK_LAUNCH("zk_sample_heads_rows");
+    return 0;
+}
+
+extern "C" int zk_eos_step_rows(const zk_gen_state* st, int prefill, int prefix_len, void* stream) {
+    ZK_REQUIRE(st != nullptr, "zk_eos_step_rows: null state");
+    ZK_REQUIRE(!st->noise_mode, "zk_eos_step_rows: a request batch takes the keyed noise only (noise_mode %d)",
+               st->noise_mode);
+    ZK_REQUIRE(st->K <= EOS_MAXK, "zk_eos_step_rows: K=%d codebooks > %d", st->K, EOS_MAXK);
+    hipLaunchKernelGGL(k_eos_step<true>, dim3(1), dim3(NT), 0, (hipStream_t)stream, *st, prefill, prefix_len);
+    ZK_CHECK_LAUNCH("zk_eos_step_rows");
     return 0;
 }
 

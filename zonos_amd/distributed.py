@@ -162,3 +162,41 @@ def generate_sharded(model, prefix_conditioning: torch.Tensor, audio_prefix_code
     else:
         allc = gather_codes(codes, device=coll_device, group=group)
     return (codes, allc) if return_local else allc
+
+
+def generate_sharded_requests(model, requests, *, group=None, gather: bool = True, uniform_shards: bool = True,
+                              coll_device=None, return_local: bool = False, **generate_kw):
+    """``generate_requests`` of a GLOBAL list of requests (zonos_amd.requests.Request) sharded over the ranks of
+    ``group``: each rank takes a contiguous block of the list (`shard`) and runs it as one request batch. A
+    request's codes depend on nothing but the request (its own seed and key), so they do not depend on the rank
+    count or on which rank runs it (within one GEMM regime).
+
+    * ``uniform_shards`` (default) pads a block that is one request short of the largest block (`padded_shard`), so
+      every rank runs the same GEMM regime and shapes. The padding is a copy of the block's last request with no
+      budget: it is independent of the real requests like any other row, so there is nothing to keep it out of
+      (no ``pad_rows``), and its codes are dropped.
+    * No collective touches the decode; with ``gather`` the one codes all_gather (`gather_codes`) returns the
+      global list in request order on every rank, else the rank's own list; ``return_local`` returns both.
+    ``model`` is a ``zonos_amd.model.Zonos`` or an engine; extra keywords (``kv_dtype``, ``weight_dtype``, ...) go to
+    the engine's ``generate_requests``. Without an initialised process group this is ``generate_requests`` on the
+    whole list."""
+    reqs = list(requests)
+    world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
+    rank = dist.get_rank(group) if world > 1 else 0
+    start, local, run = padded_shard(len(reqs), world, rank)
+    if not uniform_shards or world == 1:
+        run = local
+    engine = getattr(model, "engine", model)
+    if not reqs:
+        raise ValueError("generate_sharded_requests needs at least one request (an empty list)")
+    if local == 0:
+        codes = []
+    else:
+        mine = reqs[start:start + local]
+        mine = mine + [mine[-1]] * (run - local)
+        codes = engine.generate_requests(mine, _pad=run - local, **generate_kw)
+    if world == 1 or not gather:
+        allc = codes
+    else:
+        allc = gather_codes(codes, device=coll_device, group=group)
+    return (codes, allc) if return_local else allc

@@ -34,6 +34,7 @@ from types import SimpleNamespace
 import torch
 
 from . import _lib
+from . import requests as zrequests
 from . import sampling as zsampling
 from ._lib import GenState, SamplingParams, call, ptr
 
@@ -683,7 +684,7 @@ class HipDecoder(HipBackbone):
                              ptr(ws["part"]), ptr(ws["attn_work"]), ptr(ws["attn_cnt"]), ptr(ws["dbg"]), st, sp,
                              ptr(ws["pre_kv"][0]) if "pre_kv" in ws else None,
                              ptr(ws["pre_kv"][1]) if "pre_kv" in ws else None, ws.get("pre_smax", 0),
-                             int(bool(ws.get("w_fp8"))))
+                             int(bool(ws.get("w_fp8"))), ptr(ws.get("rows")))
 
     def _c_decode(self, ws, B, st, sp, stream):
         call("zk_decode_step", C.byref(self._step_desc(ws, B, st, sp)), stream)
@@ -716,9 +717,22 @@ class HipDecoder(HipBackbone):
         else:
             self._layers(ws, R, R, 1, False, stream, skip)
             self._heads(ws, R, 1, stream, skip)
-        call("zk_sample_heads", ptr(logits), nsp, C.byref(st), C.byref(sp), 0, 0, ptr(ws["dbg"]), stream)
-        call("zk_sample_heads", ptr(logits), nsp, C.byref(st), C.byref(sp), 0, 1, None, stream)
-        call("zk_eos_step", C.byref(st), 0, 0, stream)
+        self._sample(ws, logits, nsp, st, sp, 0, 0, stream)
+
+    def _sample(self, ws, logits, nsp, st, sp, prefill: int, prefix_len: int, stream):
+        """The step's tail: the sampler draw(s) and the EOS protocol -- batch-wide, or with a request batch
+        (ws["rows"]) the rows-mode entries on its per-utterance parameters."""
+        rows = ws.get("rows")
+        if rows is not None:
+            call("zk_sample_heads_rows", ptr(logits), nsp, C.byref(st), ptr(rows), prefill, 0, ptr(ws["dbg"]), stream)
+            if not prefill:
+                call("zk_sample_heads_rows", ptr(logits), nsp, C.byref(st), ptr(rows), 0, 1, None, stream)
+            call("zk_eos_step_rows", C.byref(st), prefill, prefix_len, stream)
+            return
+        call("zk_sample_heads", ptr(logits), nsp, C.byref(st), C.byref(sp), prefill, 0, ptr(ws["dbg"]), stream)
+        if not prefill:
+            call("zk_sample_heads", ptr(logits), nsp, C.byref(st), C.byref(sp), 0, 1, None, stream)
+        call("zk_eos_step", C.byref(st), prefill, prefix_len, stream)
 
     def _small(self, R: int) -> bool:
         # (the FP8 KV cache runs the seven-launch sequence at any batch size)
@@ -768,6 +782,33 @@ class HipDecoder(HipBackbone):
             pass
         return run.result
 
+    @torch.inference_mode()
+    def generate_requests(self, requests, *, callback=None, progress=None, poll_every: int = 16,
+                          use_graph: bool = True, trace: dict | None = None, kv_dtype: str | None = None,
+                          weight_dtype: str | None = None, _pad: int = 0) -> list:
+        """A batch of independent requests (zonos_amd.requests.Request): each with its own sampling parameters,
+        cfg_scale, seed, noise key, length budget and force_full_length. Returns one int64 [9, T_b] code tensor per
+        request: exactly what ``generate(cond_b, prefix_b, n_b, cfg_b, 1, params_b, seed=seed_b, row_base=key_b,
+        force_full_length=ffl_b)`` returns, whatever else shares the batch and whichever slot the request takes
+        (within one kernel regime: `gemm_regime`, `attn_splits_for`, the dtype options). generate()'s step on the
+        rows-mode sampler and EOS kernels (DESIGN §6 "Request batches"); keyed noise only.
+
+        Every request needs the same conditioning length and audio-prefix length. The loop runs until the last
+        request has ended: a request that ended earlier keeps its row in the launches. ValueError, before anything
+        is allocated, for an empty list, ragged prompts, cfg_scale == 1 or a repetition window outside [1, 512].
+        ``callback`` / ``progress`` / ``poll_every`` / ``use_graph`` / ``trace`` / ``kv_dtype`` / ``weight_dtype``
+        as in generate(). ``_pad``: the last ``_pad`` requests are padding (generate_sharded_requests)."""
+        plan = zrequests.plan_requests(requests, self.cfg.d_model, pad=_pad)
+        cond = zrequests.stack_conditioning(plan).to(self.device)
+        prefix = zrequests.stack_prefixes(plan)
+        r0 = plan.requests[0]
+        run = self._begin(cond, prefix, plan.max_new, r0.cfg_scale, len(plan.requests), plan.params[0], 0, 0,
+                          bool(r0.force_full_length), callback, progress, poll_every, trace, use_graph, None, "keyed",
+                          None, 0, kv_dtype, weight_dtype, rows=plan)
+        for _ in self._decode_loop(run):
+            pass
+        return run.result
+
     def stream(self, prefix_conditioning: torch.Tensor, audio_prefix_codes=None, max_new_tokens: int = 86 * 30,
                cfg_scale: float = 2.0, batch_size: int = 1, sampling_params: dict | None = None, seed: int = 0,
                row_base: int = 0, force_full_length: bool = False, progress=None, use_graph: bool = True,
@@ -802,8 +843,10 @@ class HipDecoder(HipBackbone):
 
     def _begin(self, prefix_conditioning, audio_prefix_codes, max_new_tokens, cfg_scale, batch_size, sampling_params,
                seed, row_base, force_full_length, callback, progress, poll_every, trace, use_graph, _after_prefill,
-               noise, generator, pad_rows, kv_dtype, weight_dtype) -> SimpleNamespace:
-        """generate() up to its decode loop: the refusals, the workspace, the prefill and the captured step."""
+               noise, generator, pad_rows, kv_dtype, weight_dtype, rows=None) -> SimpleNamespace:
+        """generate() up to its decode loop: the refusals, the workspace, the prefill and the captured step.
+        ``rows`` (generate_requests): the plan of a request batch (zonos_amd.requests.plan_requests) -- the
+        batch-wide sampling arguments are then those of request 0 and only feed the debug loggers."""
         assert cfg_scale != 1, "TODO: add support for cfg_scale=1"                     # model.py:247
         if batch_size * 2 != prefix_conditioning.shape[0]:                            # model.py:249-250
             raise ValueError(f"Batch size mismatch: {batch_size} * 2 != {prefix_conditioning.shape[0]}")
@@ -856,6 +899,8 @@ class HipDecoder(HipBackbone):
         codes = torch.full((B, N_CB, T), UNKNOWN, dtype=torch.int64, device=self.device)
         if audio_prefix_codes is not None:
             codes[..., :P] = audio_prefix_codes.to(self.device)
+        if rows is not None:                # per-request budgets: nothing to write past P + n_b
+            zrequests.budget_mask(codes, P, rows.budgets)
         call("zk_delay_apply", ptr(codes), B, N_CB, T, MASK, ptr(ws["delayed"]), stream)
 
         sp = SamplingParams(float(spd["temperature"]), float(spd["top_p"]), float(spd["min_p"]),
@@ -874,6 +919,13 @@ class HipDecoder(HipBackbone):
             st = self._gen_state(ws, B, seed, row_base)
         else:
             raise ValueError(f"noise must be 'keyed' or 'torch', not {noise!r}")
+        # a request batch: the device zk_row_params [B] the rows-mode sampler reads (None: the batch-wide one)
+        ws["rows"] = None
+        if rows is not None:
+            if noise != "keyed":
+                raise ValueError("a request batch samples from the keyed noise only")
+            ws["rows"] = torch.frombuffer(bytearray(bytes(zrequests.row_params(rows))),
+                                          dtype=torch.uint8).to(self.device)
         ws["scal"].zero_()
 
         # ---- prefill (model.py:297-319, _prefill 181-202)
@@ -893,9 +945,7 @@ class HipDecoder(HipBackbone):
                 self._prenorm(ws, R * S, stream, None)
             self._layers(ws, R * S, R, S, True, stream, None)
             self._heads(ws, R, S, stream, None)
-            call("zk_sample_heads", ptr(ws["part"]), ws["splits"]["heads"], C.byref(st), C.byref(sp), 1, 0,
-                 ptr(ws["dbg"]), stream)
-            call("zk_eos_step", C.byref(st), 1, P + 1, stream)
+            self._sample(ws, ws["part"], ws["splits"]["heads"], st, sp, 1, P + 1, stream)
         if _after_prefill is not None:      # test hook (teacher forcing of the first frame)
             _after_prefill(ws["delayed"][..., P + 1:P + 2])
         # Debug logging. The sampler statistics need the logits of every step (one step per poll);
@@ -921,6 +971,10 @@ class HipDecoder(HipBackbone):
         ws["stopping"].zero_()
         ws["act"].zero_()
         ws["rp"].fill_(float(spd["repetition_penalty"]))
+        if rows is not None:                # per request: remaining = n_b + 9 - 1 (model.py:335), its own penalty
+            ws["remaining"].copy_(torch.tensor([n + N_CB - 1 for n in rows.budgets], dtype=torch.int32))
+            ws["rp"].copy_(torch.tensor([float(p["repetition_penalty"]) for p in rows.params]))
+            pad_rows = rows.pad
         if pad_rows:                        # padding rows: out of the EOS protocol (docstring)
             ws["eos_mode"][B - pad_rows:] = 1
             ws["steps_after"][B - pad_rows:] = 0
@@ -943,7 +997,8 @@ class HipDecoder(HipBackbone):
                                off0=off0 if gen is not None else 0, incr=incr if gen is not None else 0,
                                force_full_length=force_full_length, callback=callback, progress=progress, trace=trace,
                                logdbg=logdbg, eosdbg=eosdbg, eos_prev=eos_prev if eosdbg else None, per_poll=per_poll,
-                               G=G, graph=graph, max_steps=max_steps, streamer=None, result=None, finished=False)
+                               G=G, graph=graph, max_steps=max_steps, streamer=None, result=None, finished=False,
+                               rows=rows)
 
     def _finish(self, run) -> torch.Tensor:
         """The end of a generation, run to its end or left early: waits for what is enqueued and advances the
@@ -1016,7 +1071,11 @@ class HipDecoder(HipBackbone):
                     yield from sm.emit(ws["delayed"], dict(pending, ev=None))
                 yield from sm.emit(ws["delayed"], sm.plan(P, offset - N_CB, True, done_steps, None))
                 sm.drain()
-            run.result = finalize(ws["delayed"], offset, P, stream)
+            if run.rows is not None:            # per-request trim; the padding requests' codes are dropped
+                run.result = zrequests.trim_request_codes(ws["delayed"], P, run.rows.budgets,
+                                                          offset)[:run.rows.real]
+            else:
+                run.result = finalize(ws["delayed"], offset, P, stream)
         except GeneratorExit:                   # the consumer left early: drain, leave torch's generator right
             self._finish(run)
             raise

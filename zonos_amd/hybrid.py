@@ -339,7 +339,8 @@ class HybridDecoder(HybridBackbone, HipDecoder):
                                C.cast(ws["hybrid_layers"], C.c_void_p), ptr(self.emb), ptr(self.heads),
                                ptr(self.lnf_w), ptr(self.lnf_b), ptr(self.freqs), ptr(ws["x"]), ptr(ws["xn"]),
                                ptr(ws["y"]), ptr(ws["h"]), ptr(ws["part"]), ptr(ws["attn_work"]), ptr(ws["yz"]),
-                               ptr(ws["ym"]), ptr(ws["xc"]), ptr(ws["dbg"]), st, sp, ptr(ws["xf"]))
+                               ptr(ws["ym"]), ptr(ws["xc"]), ptr(ws["dbg"]), st, sp, ptr(ws["xf"]),
+                               ptr(ws.get("rows")))
 
     def _c_decode(self, ws, B, st, sp, stream):
         call("zk_hybrid_decode_step", C.byref(self._step_desc(ws, B, st, sp)), stream)

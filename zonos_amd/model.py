@@ -18,6 +18,7 @@ import torch
 from .autoencoder import DACAutoencoder
 from .config import ZonosConfig
 from .engine import EngineConfig, HipDecoder
+from .requests import Request  # noqa: F401  (the public request type of generate_requests)
 from .utils import DEFAULT_DEVICE, hub_download
 
 
@@ -155,6 +156,29 @@ class Zonos:
                                    force_full_length=force_full_length, callback=callback, progress=prog,
                                    noise=noise, pad_rows=pad_rows, kv_dtype=kv_dtype,
                                    weight_dtype=weight_dtype)
+        if prog is not None:
+            prog.close()
+        return out
+
+    @torch.inference_mode()
+    def generate_requests(self, requests, progress_bar: bool = True,
+                          callback: Callable[[torch.Tensor, int, int], bool] | None = None, *,
+                          kv_dtype: str | None = None, weight_dtype: str | None = None) -> list:
+        """A batch of independent requests (``Request``: conditioning [2, Lc, D], optional audio prefix, and its own
+        max_new_tokens, cfg_scale, sampling_params, seed, key and force_full_length). Returns one [9, T_b] code
+        tensor per request, each exactly what ``generate(..., batch_size=1, seed=seed_b, row_base=key_b)`` gives
+        that request alone -- whatever else shares the batch (HipDecoder.generate_requests). Keyed noise only;
+        every request needs the same conditioning and prefix lengths."""
+        reqs = list(requests)
+        prog = None
+        if progress_bar and reqs:
+            try:
+                from tqdm import tqdm
+                prog = tqdm(total=max(int(r.max_new_tokens) for r in reqs) + 8, desc="Generating")
+            except ImportError:
+                prog = None
+        out = self.engine.generate_requests(reqs, callback=callback, progress=prog, kv_dtype=kv_dtype,
+                                            weight_dtype=weight_dtype)
         if prog is not None:
             prog.close()
         return out
