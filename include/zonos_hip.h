@@ -103,6 +103,18 @@ int zk_embed_codes(const int64_t* ids, int B, int S, int K, long ids_bstride, lo
                    void* x_out, int out_S, int out_t0, const void* ln_w, const void* ln_b, float eps,
                    void* xn_out, const int32_t* skip, void* stream);
 
+/* Prefill placement and epilogue of a request batch whose conditionings differ in length (zk_prefill_rows;
+ * the reference pads every text to the longest, conditioning.py, and attends to the pad tokens). row_off: device
+ * int32 [rows], <= 0.
+ * zk_embed_codes_rows: zk_embed_codes without col_dev, LayerNorm and skip, each row at its own position -- output
+ * row r*out_S + out_t0 + row_off[r] + t (the start clamped into [0, out_S - S] on the device), the same sum.
+ * zk_gather_last_rows: out bf16 [R][D] = x[r*S + S - 1 + row_off[r]] (offset clamped into [-(S-1), 0]): the last
+ * valid position of every row, compact, for the heads GEMM of the prefill (model.py:300-304). */
+int zk_embed_codes_rows(const int64_t* ids, int B, int S, int K, long ids_bstride, long ids_kstride,
+                        const void* emb, int V, int D, int rows_dup, void* x_out, int out_S, int out_t0,
+                        const int32_t* row_off, void* stream);
+int zk_gather_last_rows(const void* x, int R, int S, int D, const int32_t* row_off, void* out, void* stream);
+
 /* y = LayerNorm(x) (nn.LayerNorm with bias, _torch.py:88,90,62), rows x D. */
 int zk_layernorm(const void* x, const void* w, const void* b, float eps, int rows, int D,
                  void* y, void* stream);
@@ -238,6 +250,16 @@ int zk_attn_decode_qkv_sc(const float* part, int gemm_nsplit, const float* freqs
                           const int32_t* ctx_dev, float* work, int nsplit, uint32_t* counters, void* out,
                           int rope_neox, const int32_t* skip, void* stream);
 
+/* zk_attn_decode_qkv_sc with a context per row (interleaved RoPE only): workgroup (split, kv head, r) uses
+ * ctx_r = ctx0 + *ctx_dev + row_off[r], clamped into [1, Smax] on the device (row_off: device int32 [R]).
+ * RoPE row ctx_r - 1, the new key's slot, the key range of every split and the mask all follow ctx_r, so row r
+ * gets, bit for bit, what zk_attn_decode_qkv_sc gives it at that context; row_off all zero is that entry.
+ * The rows of a batch whose prompts differ in length (_torch.py:33-49 keeps one position for the batch). */
+int zk_attn_decode_qkv_sc_rows(const float* part, int gemm_nsplit, const float* freqs, void* k_cache,
+                               void* vt_cache, int R, int H, int Hkv, int hd, int Smax, int ctx0,
+                               const int32_t* ctx_dev, const int32_t* row_off, float* work, int nsplit,
+                               uint32_t* counters, void* out, const int32_t* skip, void* stream);
+
 /* zk_attn_decode_qkv for nsplit >= 2 key ranges WITHOUT the merge: leaves the split partials
  * (m, l, unnormalised O per query head) in work [R][Hkv][nsplit][8 + 4*128] fp32 for the
  * consumer, zk_gemv_attn_out, which merges them in its prologue (replaces the
@@ -283,6 +305,11 @@ int zk_attn_decode_qkv_f8(const float* part, int gemm_nsplit, const float* freqs
                           void* k_scale, void* v_scale, int R, int H, int Hkv, int hd, int Smax, int ctx0,
                           const int32_t* ctx_dev, float* work, int nsplit, uint32_t* counters, void* out,
                           const int32_t* skip, void* stream);
+/* zk_attn_decode_qkv_f8 with a context per row, as zk_attn_decode_qkv_sc_rows (_torch.py:33-49, :61-65). */
+int zk_attn_decode_qkv_f8_rows(const float* part, int gemm_nsplit, const float* freqs, void* k8, void* v8,
+                               void* k_scale, void* v_scale, int R, int H, int Hkv, int hd, int Smax, int ctx0,
+                               const int32_t* ctx_dev, const int32_t* row_off, float* work, int nsplit,
+                               uint32_t* counters, void* out, const int32_t* skip, void* stream);
 
 /* ------------------------------------------------------------------ graphs and timing
  * The decode step is captured once into a hipGraph and replayed (the reference runs the
@@ -463,6 +490,25 @@ int zk_decode_step(const zk_step_desc* d, void* stream);
  * The loop state (st.scal, eos_mode, ...) is initialised by the host afterwards (model.py:316-342).
  * Fails (-1, before any launch) unless smax >= Lc + st.Ld, the context of the last decode step. */
 int zk_prefill(const zk_step_desc* d, const void* cond, int Lc, int P, void* q, void* stream);
+
+/* The two entries above for a batch whose conditionings differ in length (a request batch, rows != NULL, is
+ * the use; the reference pads every text to the longest and attends to the pad tokens, conditioning.py). Every
+ * row is left-aligned at position 0: row r holds cond_r (Lc_r tokens), then the P + 1 embedded frames.
+ * row_off: device int32 [2B], row_off[r] = Lc_r - Lc <= 0 with Lc the longest (the cond and the uncond row of an
+ * utterance alike), fixed for the generation, so a captured step replays with it. NULL: the entries above.
+ * Row r's position at a step is st.scal[1] + row_off[r], its context one more; st.scal[1] counts from
+ * S = Lc + P + 1 as before and the descriptor's buffers and smax are sized by Lc.
+ * zk_prefill_rows: cond is bf16 [2B][Lc][D], zero-padded at the end. The frames of row r are embedded at
+ * positions Lc + row_off[r] ... (zk_embed_codes_rows), the P + 1 positions behind Lc are zeroed first, so every
+ * position behind a row's own S_r = Lc_r + P + 1 holds zeros and its keys are finite (the causal prefill
+ * computes a row's valid positions exactly as it computes them alone); the heads read each row's last valid
+ * position (zk_gather_last_rows into y). zk_decode_step_rows: zk_attn_decode_qkv_sc_rows /
+ * zk_attn_decode_qkv_f8_rows as the attention. Both fail before any launch with attn_merge > 0, with rope_neox,
+ * or in a build without those kernels. (The offsets are an argument, not a descriptor field: zk_step_desc
+ * keeps its size and `rows` stays its last field.) */
+int zk_decode_step_rows(const zk_step_desc* d, const int32_t* row_off, void* stream);
+int zk_prefill_rows(const zk_step_desc* d, const void* cond, int Lc, int P, void* q, const int32_t* row_off,
+                    void* stream);
 
 /* ------------------------------------------------------------------ hybrid decode step
  * The same two entries for the Zonos-v0.1-hybrid backbone (zonos/backbone/_mamba_ssm.py:9-57 ->

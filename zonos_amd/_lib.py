@@ -137,6 +137,10 @@ _SIGS = {
     "zk_attn_decode_qkv": [P, I, P, P, P, I, I, I, I, I, I, P, P, I, P, I, P, P],
     "zk_attn_decode_qkv_sc": [P, I, P, P, P, I, I, I, I, I, I, P, P, I, P, P, I, P, P],
     "zk_attn_decode_qkv_part": [P, I, P, P, P, I, I, I, I, I, I, P, P, I, I, P, P],
+    "zk_attn_decode_qkv_sc_rows": [P, I, P, P, P, I, I, I, I, I, I, P, P, P, I, P, P, P, P],
+    "zk_attn_decode_qkv_f8_rows": [P, I, P, P, P, P, P, I, I, I, I, I, I, P, P, P, I, P, P, P, P],
+    "zk_embed_codes_rows": [P, I, I, I, L, L, P, I, I, I, P, I, I, P, P],
+    "zk_gather_last_rows": [P, I, I, I, P, P, P],
     "zk_kv_quantize_e4m3": [P, P, I, I, I, I, I, P, P, P, P, I, P],
     "zk_attn_decode_f8": [P, P, P, P, P, I, I, I, I, I, I, P, P, I, P, P, P],
     "zk_attn_decode_qkv_f8": [P, I, P, P, P, P, P, I, I, I, I, I, I, P, P, I, P, P, P, P],
@@ -144,7 +148,9 @@ _SIGS = {
     "zk_gemv_qkv_rope": [P, P, I, I, I, I, P, P, F, P, P, P, I, P, P, P, P],
     "zk_attn_decode_q_part": [P, P, P, I, I, I, I, I, I, P, P, I, P, P],
     "zk_decode_step": [C.POINTER(StepDesc), P],
+    "zk_decode_step_rows": [C.POINTER(StepDesc), P, P],
     "zk_prefill": [C.POINTER(StepDesc), P, I, I, P, P],
+    "zk_prefill_rows": [C.POINTER(StepDesc), P, I, I, P, P, P],
     "zk_hybrid_decode_step": [C.POINTER(HybridDesc), P],
     "zk_hybrid_prefill": [C.POINTER(HybridDesc), P, I, I, P, P],
     "zk_dac_decode": [C.POINTER(DacDesc), P, I, I, P, P, C.c_size_t, P, P],

@@ -136,7 +136,9 @@ class HipZonosBackbone(nn.Module):
         lengths = inference_params.lengths_per_sample
         pos = int(lengths[0]) if lengths is not None else inference_params.seqlen_offset
         if lengths is not None:
-            assert bool((lengths == pos).all()), "rows at different positions"
+            if not bool((lengths == pos).all()):
+                raise ValueError("rows at different positions: the backbone plugin keeps one position for the "
+                                 "batch (a context per row is the engine's generate_requests(ragged=True))")
         if S > 1:
             assert pos == 0, "prefill must start at position 0 (reference SDPA is_causal semantics)"
         assert pos + S <= smax
@@ -290,7 +292,9 @@ class HipHybridBackbone(HipZonosBackbone):
         lengths = inference_params.lengths_per_sample
         pos = int(lengths[0]) if lengths is not None else inference_params.seqlen_offset
         if lengths is not None:
-            assert bool((lengths == pos).all()), "rows at different positions"
+            if not bool((lengths == pos).all()):
+                raise ValueError("rows at different positions: the backbone plugin keeps one position for the "
+                                 "batch (a context per row is the engine's generate_requests(ragged=True))")
         if S > 1:
             assert pos == 0, "prefill must start at position 0 (Mamba2.forward fills the states from zero)"
         assert not core.attn_ids or pos + S <= smax

@@ -378,11 +378,16 @@ ZK_DEV void attn_finish(AttnSmem& sm, const Bar& bar, const AttnState& st, int s
 // word is waited for, then the RoPE row and the first key blocks are requested: the prologue then waits only
 // for its own (older) loads while the key blocks stream, instead of for everything (vmcnt retires in issue
 // order), and the key loop starts while the early key blocks are still arriving.
-template <bool FUSED, bool NEOX, bool KVNT, bool COMB, int PGS, class Bar, class Issued>
+// ROWS (k_attn_decode_rows, a request batch with conditionings of different lengths): `rowr` is the raw word
+// row_off[r] (<= 0), loaded by the kernel beside the skip and the context word, and the row's context is
+// ctx0 + *ctx_dev + row_off[r], clamped into [1, Smax] (device data: a bad offset must stay in bounds).
+// Everything below derives from that one value, so a row is treated exactly as the uniform kernel treats it
+// at that context.
+template <bool FUSED, bool NEOX, bool KVNT, bool COMB, int PGS, bool ROWS, class Bar, class Issued>
 ZK_DEV void attn_decode_wg(AttnSmem& sm, const Bar& bar, const Issued& issued, int split, int nsplit, int g, int r,
                            const bf16_t* q, bf16_t* kc, bf16_t* vt, int R, int H, int Hkv, int Smax, int ctx0,
                            int cwr, float* work, float scale, bf16_t* out, const float* part, int gsplit,
-                           const float* freqs, uint32_t* cnt) {
+                           const float* freqs, uint32_t* cnt, int rowr = 0) {
     constexpr int HD = 128;
     ZK_ATT_PROF_PTR;
     ZK_ATT_STAMP(0);
@@ -412,7 +417,9 @@ ZK_DEV void attn_decode_wg(AttnSmem& sm, const Bar& bar, const Issued& issued, i
         asm volatile("" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
     }
-    const int ctx = min(ctx0 + uni(cwr), Smax);
+    int ctx;
+    if constexpr (ROWS) ctx = (int)max(1L, min((long)ctx0 + uni(cwr) + uni(rowr), (long)Smax));
+    else ctx = min(ctx0 + uni(cwr), Smax);
     if constexpr (PGS > 0) {
         const float* fc = freqs + (size_t)(ctx - 1) * HD;
 #pragma unroll
@@ -707,9 +714,30 @@ __global__ __launch_bounds__(256, 2) void k_attn_decode(const bf16_t* q, bf16_t*
     // (the context is clamped to the cache: a skipped launch after the last step may see ctx = Smax + 1,
     // and its first key blocks are loaded before the skip test; every real step has ctx <= Smax)
     const int cwr = ld_word(ctx_dev);
-    attn_decode_wg<FUSED, NEOX, KVNT, COMB, PGS>(sm, [] { __syncthreads(); }, [sk] { return uni(sk) != 0; },
-                                                blockIdx.x, gridDim.x, blockIdx.y, blockIdx.z, q, kc, vt, R, H, Hkv,
-                                                Smax, ctx0, cwr, work, scale, out, part, gsplit, freqs, cnt);
+    attn_decode_wg<FUSED, NEOX, KVNT, COMB, PGS, false>(sm, [] { __syncthreads(); }, [sk] { return uni(sk) != 0; },
+                                                       blockIdx.x, gridDim.x, blockIdx.y, blockIdx.z, q, kc, vt, R, H,
+                                                       Hkv, Smax, ctx0, cwr, work, scale, out, part, gsplit, freqs, cnt);
+}
+
+// k_attn_decode<true, false, ...> (fused, interleaved RoPE) with a context per row: workgroup (split, g, r) adds
+// row_off[r] to the batch-wide context word. A kernel of its own name around the same body, so the uniform
+// kernels keep their arguments and their code. row_off + r is a wave-uniform address; its load is issued with
+// the skip and the context word and waited for with them, where the body first needs the context.
+template <bool KVNT, bool COMB, int PGS>
+__global__ __launch_bounds__(256, 2) void k_attn_decode_rows(const bf16_t* q, bf16_t* kc, bf16_t* vt, int R, int H,
+                                                             int Hkv, int Smax, int ctx0, const int32_t* ctx_dev,
+                                                             float* work, float scale, bf16_t* out,
+                                                             const int32_t* skip, const float* part, int gsplit,
+                                                             const float* freqs, uint32_t* cnt,
+                                                             const int32_t* row_off) {
+    __shared__ AttnSmem sm;
+    const int sk = ld_word(skip);
+    const int cwr = ld_word(ctx_dev);
+    const int ro = ld_word(row_off + blockIdx.z);
+    attn_decode_wg<true, false, KVNT, COMB, PGS, true>(sm, [] { __syncthreads(); }, [sk] { return uni(sk) != 0; },
+                                                      blockIdx.x, gridDim.x, blockIdx.y, blockIdx.z, q, kc, vt, R, H,
+                                                      Hkv, Smax, ctx0, cwr, work, scale, out, part, gsplit, freqs, cnt,
+                                                      ro);
 }
 
 }  // namespace

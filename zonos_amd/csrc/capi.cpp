@@ -22,6 +22,11 @@
 // The request-batch sampler entries (sampler.hip), weak in the same way; rows_ok() refuses rows without them.
 #pragma weak zk_sample_heads_rows
 #pragma weak zk_eos_step_rows
+// The per-row-context entries (attn_rows.hip), weak in the same way; row_off_ok() refuses row_off without them.
+#pragma weak zk_attn_decode_qkv_sc_rows
+#pragma weak zk_attn_decode_qkv_f8_rows
+#pragma weak zk_embed_codes_rows
+#pragma weak zk_gather_last_rows
 
 static thread_local char g_err[1024] = "";
 
@@ -34,7 +39,7 @@ extern "C" void zk_set_error(const char* fmt, ...) {
 
 extern "C" const char* zk_last_error(void) { return g_err; }
 
-extern "C" int zk_version(void) { return 2; }
+extern "C" int zk_version(void) { return 3; }
 
 // sizeof / offsetof of the by-value ABI structs, so a binding (ctypes here) can verify its
 // layout without a GPU: which = 0 zk_sampling_params, 1 zk_gen_state, 4 ZkCondSeg, 5 ZkCondPlan,
@@ -171,9 +176,11 @@ const ZkWarm kNoWarm{nullptr, 0, 0, 0, 0};   // zk_resid_ln / zk_gemm_bf16 are t
 
 // Prefill prologue: the argument checks, the prefix conditioning and the codebook embeddings into
 // x rows [2B][S = Lc + P + 1][D]. desc_ok: the entry's own descriptor check (false for d == nullptr).
+// row_off (zk_prefill_rows, else NULL): cond is zero-padded to Lc, the frames of row r start at
+// Lc + row_off[r] and the P + 1 positions behind Lc are zeroed first (a short row's padding must be finite).
 template <class Desc>
 int prefill_prologue(const char* who, bool desc_ok, const Desc* d, const void* cond, int Lc, int P, const void* q,
-                     void* stream) {
+                     void* stream, const int32_t* row_off = nullptr) {
     if (!desc_ok || cond == nullptr || q == nullptr || Lc < 0 || P < 0) {
         zk_set_error("%s: bad arguments", who);
         return -1;
@@ -196,17 +203,33 @@ int prefill_prologue(const char* who, bool desc_ok, const Desc* d, const void* c
             return -1;
         }
     }
+    if (row_off != nullptr) {
+        hipError_t e = hipMemset2DAsync(static_cast<char*>(d->x) + Lc * row, S * row, 0, (P + 1) * row, 2 * d->B,
+                                        (hipStream_t)stream);
+        if (e != hipSuccess) {
+            zk_set_error("%s: clearing the padded positions: %s", who, hipGetErrorString(e));
+            return -1;
+        }
+        return zk_embed_codes_rows(d->st.delayed, d->B, P + 1, K, (long)d->st.Ld * K, d->st.Ld, d->emb, d->st.V,
+                                   d->d_model, 2, d->x, S, Lc, row_off, stream);
+    }
     return zk_embed_codes(d->st.delayed, d->B, P + 1, K, (long)d->st.Ld * K, d->st.Ld, nullptr, 0, d->emb, d->st.V,
                           d->d_model, 2, d->x, S, Lc, nullptr, nullptr, d->eps, nullptr, nullptr, stream);
 }
 
 // Prefill epilogue: the heads on the last position of every row (rows r*S + S-1 via lda = S*D), the
-// first sample and the first frame write
+// first sample and the first frame write. row_off: each row's last VALID position, gathered into y (free by now)
 template <class Desc>
-int prefill_epilogue(const Desc* d, int S, int P, void* stream) {
+int prefill_epilogue(const Desc* d, int S, int P, void* stream, const int32_t* row_off = nullptr) {
     const int R = 2 * d->B, D = d->d_model;
-    ZK_STEP(zk_gemm_bf16(static_cast<const char*>(d->xn) + (size_t)(S - 1) * D * 2, (long)S * D, d->heads, R,
-                         d->st.K * d->st.V, D, d->split_heads, 0, d->part, nullptr, nullptr, stream));
+    if (row_off != nullptr) {
+        ZK_STEP(zk_gather_last_rows(d->xn, R, S, D, row_off, d->y, stream));
+        ZK_STEP(zk_gemm_bf16(d->y, D, d->heads, R, d->st.K * d->st.V, D, d->split_heads, 0, d->part, nullptr, nullptr,
+                             stream));
+    } else {
+        ZK_STEP(zk_gemm_bf16(static_cast<const char*>(d->xn) + (size_t)(S - 1) * D * 2, (long)S * D, d->heads, R,
+                             d->st.K * d->st.V, D, d->split_heads, 0, d->part, nullptr, nullptr, stream));
+    }
     if (d->rows != nullptr) {   // a request batch: per-utterance parameters
         ZK_STEP(zk_sample_heads_rows(d->part, d->split_heads, &d->st, d->rows, 1, 0, d->dbg, stream));
         return zk_eos_step_rows(&d->st, 1, P + 1, stream);
@@ -246,7 +269,9 @@ int decode_tail(const Desc* d, int nsp, void* stream) {
 // The seven-launch split-K block sequence of HipBackbone._layers over M = R*S rows, xn -> xn.
 // Prefill (S positions per row): splits of 1, no skip / position words, zk_qkv_rope +
 // zk_attn_prefill as the attention, no L2 warm-up.
-int transformer_layers(const zk_step_desc* d, int R, int S, bool prefill, void* q, void* stream) {
+// row_off (zk_decode_step_rows, else NULL): the decode attention with a context per row.
+int transformer_layers(const zk_step_desc* d, int R, int S, bool prefill, void* q, void* stream,
+                       const int32_t* row_off = nullptr) {
     const int M = R * S;
     const int D = d->d_model, H = d->n_heads, Hk = d->n_kv, hd = d->head_dim, Fd = d->d_ff;
     const int Nqkv = (H + 2 * Hk) * hd;
@@ -271,10 +296,18 @@ int transformer_layers(const zk_step_desc* d, int R, int S, bool prefill, void* 
             ZK_STEP(zk_qkv_rope(d->part, 1, R, S, H, Hk, hd, d->freqs, 0, nullptr, q, L.k_cache, L.vt_cache, d->smax,
                                 nullptr, d->rope_neox, nullptr, stream));
             ZK_STEP(zk_attn_prefill(q, L.k_cache, L.vt_cache, R, S, H, Hk, hd, d->smax, d->y, stream));
+        } else if (d->kv_fp8 && row_off != nullptr) {
+            ZK_STEP(zk_attn_decode_qkv_f8_rows(d->part, sq, d->freqs, L.k_cache, L.vt_cache, L.k_scale, L.v_scale, R, H,
+                                               Hk, hd, d->smax, 1, pos, row_off, d->attn_work, d->attn_splits,
+                                               d->attn_cnt, d->y, skip, stream));
         } else if (d->kv_fp8) {
             ZK_STEP(zk_attn_decode_qkv_f8(d->part, sq, d->freqs, L.k_cache, L.vt_cache, L.k_scale, L.v_scale, R, H, Hk,
                                           hd, d->smax, 1, pos, d->attn_work, d->attn_splits, d->attn_cnt, d->y, skip,
                                           stream));
+        } else if (row_off != nullptr) {
+            ZK_STEP(zk_attn_decode_qkv_sc_rows(d->part, sq, d->freqs, L.k_cache, L.vt_cache, R, H, Hk, hd, d->smax, 1,
+                                               pos, row_off, d->attn_work, d->attn_splits, d->attn_cnt, d->y, skip,
+                                               stream));
         } else {
             ZK_STEP(zk_attn_decode_qkv_sc(d->part, sq, d->freqs, L.k_cache, L.vt_cache, R, H, Hk, hd, d->smax, 1, pos,
                                           d->attn_work, d->attn_splits, d->attn_cnt, d->y, d->rope_neox, skip,
@@ -323,6 +356,22 @@ int fp8_ok(const char* who, const zk_step_desc* d, bool prefill, int S) {
     if (prefill && (d->pre_k == nullptr || d->pre_vt == nullptr || d->pre_smax < S || d->pre_smax % 32 != 0)) {
         zk_set_error("%s: kv_fp8 needs the bf16 prefill scratch pair (pre_k, pre_vt, pre_smax=%d >= S=%d, %% 32 == 0)",
                      who, d->pre_smax, S);
+        return -1;
+    }
+    return 0;
+}
+
+// row_off (a context per row) runs the rows forms of the fused attention only; checked before the first launch
+int row_off_ok(const char* who, const zk_step_desc* d, const int32_t* row_off) {
+    if (row_off == nullptr) return 0;
+    if (&zk_attn_decode_qkv_sc_rows == nullptr || &zk_attn_decode_qkv_f8_rows == nullptr ||
+        &zk_embed_codes_rows == nullptr || &zk_gather_last_rows == nullptr) {
+        zk_set_error("%s: this build has no per-row-context kernels (row_off)", who);
+        return -1;
+    }
+    if (d->attn_merge > 0 || d->rope_neox) {
+        zk_set_error("%s: row_off runs the fused attention with interleaved RoPE only (attn_merge = %d must be 0, "
+                     "rope_neox = %d must be 0)", who, d->attn_merge, d->rope_neox);
         return -1;
     }
     return 0;
@@ -377,14 +426,17 @@ struct StepGemv {
 };
 }  // namespace
 
-extern "C" int zk_decode_step(const zk_step_desc* d, void* stream) {
+namespace {
+// zk_decode_step (row_off NULL) / zk_decode_step_rows; `who` names the entry in the error messages
+int decode_step(const char* who, const zk_step_desc* d, const int32_t* row_off, void* stream) {
     if (!step_ok(d)) {
-        zk_set_error("zk_decode_step: bad descriptor");
+        zk_set_error("%s: bad descriptor", who);
         return -1;
     }
-    ZK_STEP(rows_ok("zk_decode_step", d));
-    ZK_STEP(fp8_ok("zk_decode_step", d, false, 0));
-    ZK_STEP(w8_ok("zk_decode_step", d));
+    ZK_STEP(rows_ok(who, d));
+    ZK_STEP(fp8_ok(who, d, false, 0));
+    ZK_STEP(w8_ok(who, d));
+    ZK_STEP(row_off_ok(who, d, row_off));
     const int K = d->st.K, V = d->st.V, B = d->B, R = 2 * B;
     const int D = d->d_model, H = d->n_heads, Hk = d->n_kv, hd = d->head_dim, Fd = d->d_ff;
     const int Nqkv = (H + 2 * Hk) * hd;
@@ -398,7 +450,7 @@ extern "C" int zk_decode_step(const zk_step_desc* d, void* stream) {
                            0, d->small ? nullptr : L0.ln1_w, d->small ? nullptr : L0.ln1_b, d->eps,
                            d->small ? nullptr : d->xn, skip, stream));
     if (!d->small) {
-        ZK_STEP(transformer_layers(d, R, 1, false, nullptr, stream));
+        ZK_STEP(transformer_layers(d, R, 1, false, nullptr, stream, row_off));
         ZK_STEP(zk_gemm_bf16(d->xn, D, d->heads, R, K * V, D, d->split_heads, 0, d->part, nullptr, skip, stream));
         return decode_tail(d, d->split_heads, stream);
     }
@@ -421,9 +473,14 @@ extern "C" int zk_decode_step(const zk_step_desc* d, void* stream) {
                                                 pos, d->attn_work, d->attn_merge, d->rope_neox, skip, stream));
                 ZK_STEP(gv.attn_out(d, L, R, skip));
             } else {
-                ZK_STEP(zk_attn_decode_qkv_sc(d->part, 1, d->freqs, L.k_cache, L.vt_cache, R, H, Hk, hd, d->smax, 1,
-                                              pos, d->attn_work, d->attn_splits, d->attn_cnt, d->y, d->rope_neox,
-                                              skip, stream));
+                if (row_off != nullptr)
+                    ZK_STEP(zk_attn_decode_qkv_sc_rows(d->part, 1, d->freqs, L.k_cache, L.vt_cache, R, H, Hk, hd,
+                                                       d->smax, 1, pos, row_off, d->attn_work, d->attn_splits,
+                                                       d->attn_cnt, d->y, skip, stream));
+                else
+                    ZK_STEP(zk_attn_decode_qkv_sc(d->part, 1, d->freqs, L.k_cache, L.vt_cache, R, H, Hk, hd, d->smax, 1,
+                                                  pos, d->attn_work, d->attn_splits, d->attn_cnt, d->y, d->rope_neox,
+                                                  skip, stream));
                 ZK_STEP(gv.fused(d->y, H * hd, L.wo, L.wo8, L.wo_scale, R, D, H * hd, 2, nullptr, nullptr, d->eps,
                                  nullptr, d->x, skip));
             }
@@ -439,14 +496,35 @@ extern "C" int zk_decode_step(const zk_step_desc* d, void* stream) {
     return decode_tail(d, 1, stream);
 }
 
-extern "C" int zk_prefill(const zk_step_desc* d, const void* cond, int Lc, int P, void* q, void* stream) {
-    if (step_ok(d)) ZK_STEP(rows_ok("zk_prefill", d));
-    if (step_ok(d)) ZK_STEP(fp8_ok("zk_prefill", d, true, Lc + P + 1));
-    ZK_STEP(prefill_prologue("zk_prefill", step_ok(d), d, cond, Lc, P, q, stream));
+// zk_prefill (row_off NULL) / zk_prefill_rows
+int prefill(const char* who, const zk_step_desc* d, const void* cond, int Lc, int P, void* q, const int32_t* row_off,
+            void* stream) {
+    if (step_ok(d)) ZK_STEP(rows_ok(who, d));
+    if (step_ok(d)) ZK_STEP(fp8_ok(who, d, true, Lc + P + 1));
+    if (step_ok(d)) ZK_STEP(row_off_ok(who, d, row_off));
+    ZK_STEP(prefill_prologue(who, step_ok(d), d, cond, Lc, P, q, stream, row_off));
     const int R = 2 * d->B, S = Lc + P + 1;
     ZK_STEP(zk_layernorm(d->x, d->layers[0].ln1_w, d->layers[0].ln1_b, d->eps, R * S, d->d_model, d->xn, stream));
     ZK_STEP(transformer_layers(d, R, S, true, q, stream));
-    return prefill_epilogue(d, S, P, stream);
+    return prefill_epilogue(d, S, P, stream, row_off);
+}
+}  // namespace
+
+extern "C" int zk_decode_step(const zk_step_desc* d, void* stream) {
+    return decode_step("zk_decode_step", d, nullptr, stream);
+}
+
+extern "C" int zk_decode_step_rows(const zk_step_desc* d, const int32_t* row_off, void* stream) {
+    return decode_step("zk_decode_step_rows", d, row_off, stream);
+}
+
+extern "C" int zk_prefill(const zk_step_desc* d, const void* cond, int Lc, int P, void* q, void* stream) {
+    return prefill("zk_prefill", d, cond, Lc, P, q, nullptr, stream);
+}
+
+extern "C" int zk_prefill_rows(const zk_step_desc* d, const void* cond, int Lc, int P, void* q, const int32_t* row_off,
+                               void* stream) {
+    return prefill("zk_prefill_rows", d, cond, Lc, P, q, row_off, stream);
 }
 
 // ------------------------------------------------------------------ hybrid step (zonos_amd.hybrid)

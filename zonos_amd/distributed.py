@@ -177,8 +177,9 @@ def generate_sharded_requests(model, requests, *, group=None, gather: bool = Tru
       (no ``pad_rows``), and its codes are dropped.
     * No collective touches the decode; with ``gather`` the one codes all_gather (`gather_codes`) returns the
       global list in request order on every rank, else the rank's own list; ``return_local`` returns both.
-    ``model`` is a ``zonos_amd.model.Zonos`` or an engine; extra keywords (``kv_dtype``, ``weight_dtype``, ...) go to
-    the engine's ``generate_requests``. Without an initialised process group this is ``generate_requests`` on the
+    ``model`` is a ``zonos_amd.model.Zonos`` or an engine; extra keywords (``kv_dtype``, ``weight_dtype``, ``ragged``,
+    ...) go to the engine's ``generate_requests``. With ``ragged=True`` (conditionings of different lengths) every
+    shard is a ragged batch of its own: it pads to the longest conditioning of ITS requests. Without an initialised process group this is ``generate_requests`` on the
     whole list."""
     reqs = list(requests)
     world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1

@@ -472,9 +472,14 @@ class HipBackbone:
                          ws["smax"], 1, ptr(scal[1:2]), ptr(ws["attn_work"]), merge, self.rope_neox, skip, stream)
                     call(attn_out, ptr(ws["attn_work"]), merge, Hk, *W(L, "wo"), R, D, H * hd, ptr(x), skip, stream)
                 else:
-                    call("zk_attn_decode_qkv_sc", ptr(part), 1, ptr(self.freqs), ptr(kc), ptr(vt), R, H, Hk, hd,
-                         ws["smax"], 1, ptr(scal[1:2]), ptr(ws["attn_work"]), ws["attn_splits"],
-                         ptr(ws["attn_cnt"]), ptr(y), self.rope_neox, skip, stream)
+                    if ws.get("row_off") is not None:    # a ragged request batch: a context per row
+                        call("zk_attn_decode_qkv_sc_rows", ptr(part), 1, ptr(self.freqs), ptr(kc), ptr(vt), R, H, Hk,
+                             hd, ws["smax"], 1, ptr(scal[1:2]), ptr(ws["row_off"]), ptr(ws["attn_work"]),
+                             ws["attn_splits"], ptr(ws["attn_cnt"]), ptr(y), skip, stream)
+                    else:
+                        call("zk_attn_decode_qkv_sc", ptr(part), 1, ptr(self.freqs), ptr(kc), ptr(vt), R, H, Hk, hd,
+                             ws["smax"], 1, ptr(scal[1:2]), ptr(ws["attn_work"]), ws["attn_splits"],
+                             ptr(ws["attn_cnt"]), ptr(y), self.rope_neox, skip, stream)
                     call(fused, ptr(y), H * hd, *W(L, "wo"), R, D, H * hd, 2, None, None, c.eps, None,
                          ptr(x), skip, stream)
             call(fused, ptr(x), D, *W(L, "fc1"), R, 2 * Fd, D, 1, ptr(L["ln2_w"]), ptr(L["ln2_b"]),
@@ -505,6 +510,9 @@ class HipBackbone:
         x, xn, q, y, h, part = ws["x"], ws["xn"], ws["q"], ws["y"], ws["h"], ws["part"]
         scal = ws["scal"]
         pos_dev = None if prefill else ptr(scal[1:2])
+        row_off = ws.get("row_off")          # a ragged request batch: the decode attention with a context per row
+        if row_off is not None and not prefill and (self.rope_neox or not self.fuse_qkv):
+            raise ValueError("a context per row runs the fused decode attention with interleaved RoPE only")
         for i, L in enumerate(self.layers):
             fp8 = bool(ws.get("kv_fp8"))
             kc, vt, ksc, vsc = self._kv8(ws, i) if fp8 else (*self._kv(ws, i), None, None)
@@ -517,6 +525,10 @@ class HipBackbone:
                 call("zk_attn_prefill", ptr(q), ptr(pk), ptr(pv), R, S, H, Hk, hd, ws["pre_smax"], ptr(y), stream)
                 call("zk_kv_quantize_e4m3", ptr(pk), ptr(pv), R, Hk, hd, S, ws["pre_smax"], ptr(kc), ptr(vt), ptr(ksc),
                      ptr(vsc), ws["smax"], stream)
+            elif fp8 and row_off is not None:
+                call("zk_attn_decode_qkv_f8_rows", ptr(part), sp["qkv"], ptr(self.freqs), ptr(kc), ptr(vt), ptr(ksc),
+                     ptr(vsc), R, H, Hk, hd, ws["smax"], 1, ptr(scal[1:2]), ptr(row_off), ptr(ws["attn_work"]),
+                     ws["attn_splits"], ptr(ws["attn_cnt"]), ptr(y), skip, stream)
             elif fp8:
                 call("zk_attn_decode_qkv_f8", ptr(part), sp["qkv"], ptr(self.freqs), ptr(kc), ptr(vt), ptr(ksc),
                      ptr(vsc), R, H, Hk, hd, ws["smax"], 1, ptr(scal[1:2]), ptr(ws["attn_work"]), ws["attn_splits"],
@@ -525,6 +537,10 @@ class HipBackbone:
                 call("zk_qkv_rope", ptr(part), sp["qkv"], R, S, H, Hk, hd, ptr(self.freqs), 0, pos_dev, ptr(q),
                      ptr(kc), ptr(vt), ws["smax"], None, self.rope_neox, skip, stream)
                 call("zk_attn_prefill", ptr(q), ptr(kc), ptr(vt), R, S, H, Hk, hd, ws["smax"], ptr(y), stream)
+            elif row_off is not None:
+                call("zk_attn_decode_qkv_sc_rows", ptr(part), sp["qkv"], ptr(self.freqs), ptr(kc), ptr(vt), R, H, Hk,
+                     hd, ws["smax"], 1, ptr(scal[1:2]), ptr(row_off), ptr(ws["attn_work"]), ws["attn_splits"],
+                     ptr(ws["attn_cnt"]), ptr(y), skip, stream)
             elif self.fuse_qkv:
                 # in_proj epilogue fused into the attention launch (position = ctx - 1 = scal[1])
                 # split partials (long contexts at small batch) merged inside the launch
@@ -563,6 +579,7 @@ class HipDecoder(HipBackbone):
     _fp8 = False                    # the running generate() uses the FP8 KV cache
     w_fp8_supported = True          # generate(weight_dtype="fp8"): the transformer backbone's small-batch path only
     _w8 = False                     # the running generate() uses the FP8 layer weights
+    ragged_supported = True         # generate_requests(ragged=True) with differing lengths: the transformer backbone only
 
     def __init__(self, cfg: EngineConfig, weights: dict, device="cuda"):
         super().__init__(cfg, weights, device)
@@ -599,14 +616,15 @@ class HipDecoder(HipBackbone):
         return dict(kv=torch.zeros(c.n_layer, 2, R * c.n_kv * smax * c.head_dim, dtype=torch.bfloat16, device=dev),
                     attn_cnt=cnt)
 
-    def _alloc(self, B: int, Lc: int, P: int, max_new: int):
+    def _alloc(self, B: int, Lc: int, P: int, max_new: int, ragged: bool = False):
         R = 2 * B
         T = P + max_new
         Ld = T + N_CB
         seq_len = Lc + T + N_CB
         smax = -(-seq_len // ATTN_CHUNK) * ATTN_CHUNK
         S_pre = Lc + P + 1
-        key = (B, Lc, P, max_new, "fp8" if self._fp8 else "bf16", "w8" if self._w8 else "w16")
+        key = (B, Lc, P, max_new, "ragged" if ragged else "uniform", "fp8" if self._fp8 else "bf16",
+               "w8" if self._w8 else "w16")
         if self._ws is not None and self._ws["key"] == key:
             ws = self._ws
             for k in ws["state_keys"]:
@@ -646,9 +664,13 @@ class HipDecoder(HipBackbone):
             pass
 
     def _heads(self, ws, R: int, S: int, stream, skip):
-        """Heads GEMM on the last position of every row -> split-K slabs in ws['part']."""
+        """Heads GEMM on the last position of every row -> split-K slabs in ws['part']. The prefill of a ragged
+        request batch (S > 1, ws["row_off"]): on each row's last VALID position, gathered into ws["y"]."""
         D = self.cfg.d_model
         last = ws["xn"][S - 1:]           # rows r*S + S-1 via lda = S*D
+        if S > 1 and ws.get("row_off") is not None:
+            call("zk_gather_last_rows", ptr(ws["xn"]), R, S, D, ptr(ws["row_off"]), ptr(ws["y"]), stream)
+            last, S = ws["y"], 1
         call("zk_gemm_bf16", ptr(last), S * D, ptr(self.heads), R, N_CB * VOCAB, D, ws["splits"]["heads"], 0,
              ptr(ws["part"]), None, skip, stream)
 
@@ -687,9 +709,16 @@ class HipDecoder(HipBackbone):
                              int(bool(ws.get("w_fp8"))), ptr(ws.get("rows")))
 
     def _c_decode(self, ws, B, st, sp, stream):
+        if ws.get("row_off") is not None:   # a ragged request batch: the same sequence with a context per row
+            call("zk_decode_step_rows", C.byref(self._step_desc(ws, B, st, sp)), ptr(ws["row_off"]), stream)
+            return
         call("zk_decode_step", C.byref(self._step_desc(ws, B, st, sp)), stream)
 
     def _c_prefill(self, ws, B, st, sp, cond, Lc, P, stream):
+        if ws.get("row_off") is not None:
+            call("zk_prefill_rows", C.byref(self._step_desc(ws, B, st, sp)), ptr(cond), Lc, P, ptr(ws["q"]),
+                 ptr(ws["row_off"]), stream)
+            return
         call("zk_prefill", C.byref(self._step_desc(ws, B, st, sp)), ptr(cond), Lc, P, ptr(ws["q"]), stream)
 
     def _decode_step(self, ws, B, st, sp, stream):
@@ -785,7 +814,8 @@ class HipDecoder(HipBackbone):
     @torch.inference_mode()
     def generate_requests(self, requests, *, callback=None, progress=None, poll_every: int = 16,
                           use_graph: bool = True, trace: dict | None = None, kv_dtype: str | None = None,
-                          weight_dtype: str | None = None, _pad: int = 0) -> list:
+                          weight_dtype: str | None = None, ragged: bool = False, _pad: int = 0,
+                          _pad_fill: float = 0.0) -> list:
         """A batch of independent requests (zonos_amd.requests.Request): each with its own sampling parameters,
         cfg_scale, seed, noise key, length budget and force_full_length. Returns one int64 [9, T_b] code tensor per
         request: exactly what ``generate(cond_b, prefix_b, n_b, cfg_b, 1, params_b, seed=seed_b, row_base=key_b,
@@ -793,18 +823,28 @@ class HipDecoder(HipBackbone):
         (within one kernel regime: `gemm_regime`, `attn_splits_for`, the dtype options). generate()'s step on the
         rows-mode sampler and EOS kernels (DESIGN §6 "Request batches"); keyed noise only.
 
-        Every request needs the same conditioning length and audio-prefix length. The loop runs until the last
+        Every request needs the same audio-prefix length and, unless ``ragged=True``, the same conditioning length.
+        ``ragged=True``: conditionings of different lengths, each row left-aligned with its own KV position and
+        context (DESIGN §6 "Ragged request batches") -- no pad token is attended to, and the statement above holds
+        for the request with ITS conditioning. Transformer backbone with interleaved RoPE only; with equal lengths
+        it is the default path. The loop runs until the last
         request has ended: a request that ended earlier keeps its row in the launches. ValueError, before anything
         is allocated, for an empty list, ragged prompts, cfg_scale == 1 or a repetition window outside [1, 512].
         ``callback`` / ``progress`` / ``poll_every`` / ``use_graph`` / ``trace`` / ``kv_dtype`` / ``weight_dtype``
-        as in generate(). ``_pad``: the last ``_pad`` requests are padding (generate_sharded_requests)."""
-        plan = zrequests.plan_requests(requests, self.cfg.d_model, pad=_pad)
-        cond = zrequests.stack_conditioning(plan).to(self.device)
+        as in generate(). ``_pad``: the last ``_pad`` requests are padding (generate_sharded_requests).
+        ``_pad_fill`` (test hook): the value written in place of zero into the padding of a ragged batch -- the
+        padded conditioning and, where this class issues the prefill itself (c_step False), the positions of x
+        behind it; zk_prefill_rows zeroes those itself."""
+        plan = zrequests.plan_requests(requests, self.cfg.d_model, pad=_pad, ragged=ragged)
+        if plan.row_off is not None and not (self.ragged_supported and not self.rope_neox):
+            raise ValueError(f"ragged=True with conditionings of different lengths needs the transformer backbone "
+                             f"with interleaved RoPE ({type(self).__name__}); equal lengths run everywhere")
+        cond = zrequests.stack_conditioning(plan, _pad_fill).to(self.device)
         prefix = zrequests.stack_prefixes(plan)
         r0 = plan.requests[0]
         run = self._begin(cond, prefix, plan.max_new, r0.cfg_scale, len(plan.requests), plan.params[0], 0, 0,
                           bool(r0.force_full_length), callback, progress, poll_every, trace, use_graph, None, "keyed",
-                          None, 0, kv_dtype, weight_dtype, rows=plan)
+                          None, 0, kv_dtype, weight_dtype, rows=plan, pad_fill=_pad_fill)
         for _ in self._decode_loop(run):
             pass
         return run.result
@@ -843,7 +883,7 @@ class HipDecoder(HipBackbone):
 
     def _begin(self, prefix_conditioning, audio_prefix_codes, max_new_tokens, cfg_scale, batch_size, sampling_params,
                seed, row_base, force_full_length, callback, progress, poll_every, trace, use_graph, _after_prefill,
-               noise, generator, pad_rows, kv_dtype, weight_dtype, rows=None) -> SimpleNamespace:
+               noise, generator, pad_rows, kv_dtype, weight_dtype, rows=None, pad_fill=0.0) -> SimpleNamespace:
         """generate() up to its decode loop: the refusals, the workspace, the prefill and the captured step.
         ``rows`` (generate_requests): the plan of a request batch (zonos_amd.requests.plan_requests) -- the
         batch-wide sampling arguments are then those of request 0 and only feed the debug loggers."""
@@ -890,7 +930,10 @@ class HipDecoder(HipBackbone):
         if live is not None:                # a stream() left unfinished works in the buffers this call takes over
             self._streaming = None
             live.close()
-        ws = self._alloc(B, Lc, P, max_new_tokens)
+        row_off = getattr(rows, "row_off", None)        # a ragged request batch (plan_requests)
+        ws = self._alloc(B, Lc, P, max_new_tokens, ragged=row_off is not None)
+        # each row's context offset Lc_b - Lc, on the device for the whole generation (the captured step reads it)
+        ws["row_off"] = None if row_off is None else torch.tensor(row_off, dtype=torch.int32, device=self.device)
         stream = _lib.stream_ptr(self.device)
         T, Ld, S = ws["T"], ws["Ld"], ws["S_pre"]
         D = c.d_model
@@ -935,8 +978,13 @@ class HipDecoder(HipBackbone):
         else:
             x = ws["x"][: R * S].view(R, S, D)
             x[:, :Lc].copy_(prefix_conditioning.to(torch.bfloat16))
-            call("zk_embed_codes", ptr(ws["delayed"]), B, P + 1, N_CB, Ld * N_CB, Ld, None, 0, ptr(self.emb), VOCAB,
-                 D, 2, ptr(ws["x"]), S, Lc, None, None, c.eps, None, None, stream)
+            if ws["row_off"] is not None:   # frames at Lc_b ...; the positions behind a row's own S_b hold zeros
+                x[:, Lc:].fill_(pad_fill)
+                call("zk_embed_codes_rows", ptr(ws["delayed"]), B, P + 1, N_CB, Ld * N_CB, Ld, ptr(self.emb), VOCAB,
+                     D, 2, ptr(ws["x"]), S, Lc, ptr(ws["row_off"]), stream)
+            else:
+                call("zk_embed_codes", ptr(ws["delayed"]), B, P + 1, N_CB, Ld * N_CB, Ld, None, 0, ptr(self.emb),
+                     VOCAB, D, 2, ptr(ws["x"]), S, Lc, None, None, c.eps, None, None, stream)
             L0 = self.layers[0]
             if self.embed_norm:
                 call("zk_layernorm", ptr(ws["x"]), ptr(L0["ln1_w"]), ptr(L0["ln1_b"]), c.eps, R * S, D,

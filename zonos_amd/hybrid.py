@@ -287,6 +287,7 @@ class HybridDecoder(HybridBackbone, HipDecoder):
     small_batch_path = False      # the hybrid block sequence has its own _layers (prenorm add + norm)
     kv_fp8_supported = False      # generate(kv_dtype="fp8") raises ValueError: transformer backbone only
     w_fp8_supported = False       # generate(weight_dtype="fp8") raises ValueError likewise
+    ragged_supported = False      # generate_requests(ragged=True) with differing lengths raises ValueError likewise
     # the step / prefill sequences are enqueued by the C ABI (zk_hybrid_decode_step / zk_hybrid_prefill);
     # False issues the same sequence from Python (bit-identical; the reference for the test)
     c_step = True

@@ -163,12 +163,14 @@ class Zonos:
     @torch.inference_mode()
     def generate_requests(self, requests, progress_bar: bool = True,
                           callback: Callable[[torch.Tensor, int, int], bool] | None = None, *,
-                          kv_dtype: str | None = None, weight_dtype: str | None = None) -> list:
+                          kv_dtype: str | None = None, weight_dtype: str | None = None,
+                          ragged: bool = False) -> list:
         """A batch of independent requests (``Request``: conditioning [2, Lc, D], optional audio prefix, and its own
         max_new_tokens, cfg_scale, sampling_params, seed, key and force_full_length). Returns one [9, T_b] code
         tensor per request, each exactly what ``generate(..., batch_size=1, seed=seed_b, row_base=key_b)`` gives
         that request alone -- whatever else shares the batch (HipDecoder.generate_requests). Keyed noise only;
-        every request needs the same conditioning and prefix lengths."""
+        every request needs the same prefix length and, unless ``ragged=True`` (transformer backbone: each row then
+        keeps its own KV position, no pad token is attended to), the same conditioning length."""
         reqs = list(requests)
         prog = None
         if progress_bar and reqs:
@@ -178,7 +180,7 @@ class Zonos:
             except ImportError:
                 prog = None
         out = self.engine.generate_requests(reqs, callback=callback, progress=prog, kv_dtype=kv_dtype,
-                                            weight_dtype=weight_dtype)
+                                            weight_dtype=weight_dtype, ragged=ragged)
         if prog is not None:
             prog.close()
         return out

@@ -50,11 +50,17 @@ def _prefix(req: Request):
     return p
 
 
-def plan_requests(requests, d_model: int | None = None, pad: int = 0) -> SimpleNamespace:
+def plan_requests(requests, d_model: int | None = None, pad: int = 0, ragged: bool = False) -> SimpleNamespace:
     """Validate a list of requests and lay out what the engine needs, without touching a device. Raises ValueError
     for an empty list, ragged prompts (conditionings of different Lc, prefixes of different P), cfg_scale == 1, a
     repetition window outside the sampler's, a malformed tensor or a budget below 1. ``pad``: the last ``pad``
-    requests are padding (generate_sharded_requests' uniform shards): no budget, out of the EOS protocol."""
+    requests are padding (generate_sharded_requests' uniform shards): no budget, out of the EOS protocol.
+
+    ``ragged=True`` accepts conditionings of different lengths (prefix lengths must still agree, and every Lc_b must
+    be >= 1): ``Lc`` is then the longest, ``lcs`` the length of each request and ``row_off`` the int32 list [2B] of
+    Lc_b - Lc <= 0, the cond rows and then the uncond rows as `stack_conditioning` orders them -- what the engine
+    keeps on the device as each row's context offset (DESIGN §6 "Ragged request batches"). ``row_off`` is None when
+    all lengths agree: the batch then takes the uniform path."""
     from .engine import check_sampling_params
     reqs = list(requests)
     if not reqs:
@@ -81,13 +87,23 @@ def plan_requests(requests, d_model: int | None = None, pad: int = 0) -> SimpleN
         prefixes.append(_prefix(r))
     Lcs = {int(r.conditioning.shape[1]) for r in reqs}
     Ps = {0 if p is None else int(p.shape[1]) for p in prefixes}
-    if len(Lcs) > 1 or len(Ps) > 1:
+    if len(Ps) > 1 or (len(Lcs) > 1 and not ragged):
         raise ValueError(f"ragged prompts are not supported: every request of a batch needs the same conditioning "
-                         f"length and audio-prefix length (Lc in {sorted(Lcs)}, P in {sorted(Ps)})")
+                         f"length and audio-prefix length (Lc in {sorted(Lcs)}, P in {sorted(Ps)}); "
+                         f"generate_requests(..., ragged=True) takes conditionings of different lengths, "
+                         f"audio prefixes of different lengths never")
+    lcs = [int(r.conditioning.shape[1]) for r in reqs]
+    Lc = max(lcs)
+    row_off = None
+    if len(Lcs) > 1:
+        if min(lcs) < 1:
+            raise ValueError(f"request {lcs.index(min(lcs))}: a ragged batch needs a conditioning of at least one "
+                             f"token per request (Lc in {sorted(Lcs)})")
+        row_off = [lc - Lc for lc in lcs] * 2
     real = len(reqs) - pad
     budgets = [int(r.max_new_tokens) if i < real else 0 for i, r in enumerate(reqs)]
-    return SimpleNamespace(requests=reqs, params=params, prefixes=prefixes, Lc=Lcs.pop(), P=Ps.pop(), budgets=budgets,
-                           max_new=max(budgets), pad=pad, real=real)
+    return SimpleNamespace(requests=reqs, params=params, prefixes=prefixes, Lc=Lc, P=Ps.pop(), budgets=budgets,
+                           max_new=max(budgets), pad=pad, real=real, lcs=lcs, row_off=row_off)
 
 
 def row_params(plan):
@@ -102,9 +118,12 @@ def row_params(plan):
     return arr
 
 
-def stack_conditioning(plan) -> torch.Tensor:
-    """[cond rows | uncond rows]: the [2B, Lc, D] layout of prepare_conditioning (model.py:213-218)."""
+def stack_conditioning(plan, pad_fill: float = 0.0) -> torch.Tensor:
+    """[cond rows | uncond rows]: the [2B, Lc, D] layout of prepare_conditioning (model.py:213-218). A ragged plan
+    pads every conditioning at the end to plan.Lc with zeros (``pad_fill``: the engine's test hook)."""
     cs = [r.conditioning for r in plan.requests]
+    if plan.row_off is not None:
+        cs = [torch.cat([c, c.new_full((2, plan.Lc - c.shape[1], c.shape[2]), pad_fill)], dim=1) for c in cs]
     return torch.cat([c[0:1] for c in cs] + [c[1:2] for c in cs])
 
 
