@@ -143,6 +143,19 @@ int zk_gemm_bf16(const void* A, long lda, const void* W, int M, int N, int K, in
  * this decode GEMM (warm.h: issued by the kernel before it) reads; 0 when the GEMM is not warmed.
  * Never more than ceil(N / 16), the tiles of the packed image that hold a column < N. */
 int zk_gemm_warm_tiles(int M, int N, int K, int nsplit, int mode, int chunks);
+/* The launch plan of zk_gemm_bf16(M, N, K, nsplit, mode), by the entry's own shape checks (with lda = K) and
+ * the plan it launches from. Host only: no GPU is touched. Fills plan[ZK_GEMM_PLAN_N]; fields that do not
+ * belong to the family are 0:
+ *   0 family (0 k_gemv_rk, 1 k_gemm_ws, 2 k_gemm_pf, 3 k_gemm)
+ *   1 ks (k_gemv_rk: k-steps of 32 per wave)        2 pf (k_gemv_rk: k-steps, k_gemm_ws: chunks in flight)
+ *   3 nchunks (k_gemm_ws, k_gemm: 64-deep chunks of a K slice)
+ *   4 mt (k_gemm_ws: 16-row tiles)                  5 ncw (k_gemm_ws: compute waves = 16-column tiles)
+ *   6 u (k_gemm: ring slots)                        7 ntw (k_gemm: 16-column tiles per wave)
+ *   8, 9, 10 grid x, y, z   11 threads per workgroup   12 dynamic LDS bytes
+ *   13 k_gemm_pf: columns of its 256-row tile
+ * Returns 0, or -1 with zk_last_error set where the entry would refuse the shape. */
+#define ZK_GEMM_PLAN_N 14
+int zk_gemm_plan(int M, int N, int K, int nsplit, int mode, int32_t* plan);
 /* Small-batch (M <= 16) GEMV without split-K, for the B <= 8 decode layer (five launches per
  * transformer block instead of seven; replaces the k_resid_ln launches of _torch.py:100-101):
  *   ln_w/ln_b non-NULL: A holds the residual rows x (bf16, K = D = 2048) and every workgroup
@@ -155,6 +168,15 @@ int zk_gemm_warm_tiles(int M, int N, int K, int nsplit, int mode, int chunks);
 int zk_gemv_fused(const void* A, long lda, const void* W, int M, int N, int K, int mode,
                   const void* ln_w, const void* ln_b, float eps, float* Cf, void* Cb,
                   const int32_t* skip, void* stream);
+/* The launch plan of zk_gemv_fused(M, N, K, mode, ln: with the LayerNorm prologue or not), by the entry's own
+ * shape checks (with lda = K). Host only: no GPU is touched. Fills plan[ZK_GEMV_PLAN_N]:
+ *   0 lay (0 half a 16-column tile per workgroup, 1 one tile, 2 two tiles)
+ *   1 ksw (K / 32)   2 xr (rows of the LDS activation image: 2 or 16)   3 workgroups   4 threads per workgroup
+ *   5 ntw (tiles per workgroup)   6 half (0 / 1)   7 nw (waves splitting K)   8 ks (k-steps per wave)
+ *   9 pf (weight loads in flight per wave)
+ * Returns 0, or -1 with zk_last_error set where the entry would refuse the shape. */
+#define ZK_GEMV_PLAN_N 10
+int zk_gemv_plan(int M, int N, int K, int mode, int ln, int32_t* plan);
 /* Attention out_proj of a small decode batch (M = 2B <= 2 rows) straight from the split
  * partials of zk_attn_decode_qkv_part: x[M][N] = bf16(x + bf16(merge(work) . W^T))
  * (_torch.py:66 + the residual add of :100), the merge being k_attn_combine's arithmetic

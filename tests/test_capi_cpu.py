@@ -206,6 +206,91 @@ def test_dac_conv_plan_of_product_and_test_shapes(lib):
     assert plan(Cin=96, Cout=96, ks=7, dil=10)[0] == 0               # (ks - 1) * dil = 60 <= 64
 
 
+def test_gemm_and_gemv_plans_of_product_and_test_shapes(lib):
+    """zk_gemm_plan / zk_gemv_plan (the plans zk_gemm_bf16 / zk_gemv_fused launch by) for shapes of the c3 model's
+    decode and prefill and for the regime boundaries, each evaluated by hand from gemm_plan / gemv_plan / ws_ncw /
+    gf_form of gemm.hip; what the entries refuse, the queries refuse."""
+    import ctypes as C
+    for fn, n in ((lib.zk_gemm_plan, 5), (lib.zk_gemv_plan, 5)):
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_int] * n + [C.POINTER(C.c_int32)]
+    lib.zk_last_error.restype = C.c_char_p
+    RK, WS, PF, TILE = 0, 1, 2, 3
+    GF = ("family", "ks", "pf", "nchunks", "mt", "ncw", "u", "ntw", "gx", "gy", "gz", "block", "lds", "pf_cols")
+    VF = ("lay", "ksw", "xr", "grid", "block", "ntw", "half", "nw", "ks", "pf")
+
+    def gemm(M, N, K, nsplit=1, mode=0):
+        out = (C.c_int32 * 14)()
+        return lib.zk_gemm_plan(M, N, K, nsplit, mode, out), dict(zip(GF, out))
+
+    def gemv(M, N, K, mode=0, ln=0):
+        out = (C.c_int32 * 10)()
+        return lib.zk_gemv_plan(M, N, K, mode, ln, out), dict(zip(VF, out))
+
+    def ws(nch, mt, ncw, gx, gz, mode=0):           # block: ncw compute + loader waves; LDS: 6 slots of mt*16 x 64 bf16
+        nld = {(4, 8): 4, (4, 4): 4, (4, 2): 4, (4, 1): 4, (2, 8): 4, (3, 8): 4, (5, 8): 2}[(ncw, mt)]
+        return dict(family=WS, pf=4 if mode else 3, nchunks=nch, mt=mt, ncw=ncw, gx=gx, gy=1, gz=gz,
+                    block=64 * (ncw + nld), lds=6 * mt * 16 * 64 * 2)
+
+    rows = [
+        # decode, B = 64 (128 rows): in_proj split 8, out_proj split 4 (128 workgroups of 4 waves -> 256 of 2),
+        # the heads (N = 9234, split 2: 290 -> 232 workgroups of 5 waves), the SwiGLU fc1
+        ((128, 3072, 2048, 8), ws(4, 8, 4, 48, 8)),
+        ((128, 2048, 2048, 4), ws(8, 8, 2, 64, 4)),
+        ((128, 9234, 2048, 2), ws(16, 8, 5, 116, 2)),
+        ((128, 16384, 2048, 1, 1), ws(32, 8, 4, 256, 1, mode=1)),
+        ((17, 80, 256, 2), ws(2, 2, 4, 2, 2)), ((64, 80, 128, 1), ws(2, 4, 4, 2, 1)),
+        # M <= 16: the register-stream GEMV, 2 tiles per workgroup; a slice it has no form for (mode 1, 4 chunks)
+        ((16, 80, 256, 1), dict(family=RK, ks=2, pf=2, gx=3, gz=1, block=256, lds=0)),
+        ((1, 3072, 2048, 2), dict(family=RK, ks=8, pf=8, gx=96, gz=2, block=256)),
+        ((16, 112, 256, 1, 1), ws(4, 1, 4, 2, 1, mode=1)),
+        # prefill: 256-row tiles from 256 of them, else k_gemm (two tiles per wave for mode 0 slabs, N >= 512)
+        ((16400, 4096, 1024, 1), dict(family=PF, gx=65 * 16, block=512, pf_cols=256)),
+        ((9000, 8256, 512, 1, 1), dict(family=PF, gx=36 * 33, pf_cols=256)),
+        ((129, 80, 256, 1), dict(family=TILE, u=4, ntw=1, nchunks=4, gx=2, gy=2, gz=1, block=256)),
+        ((2048, 384, 2048, 1), dict(family=TILE, u=4, ntw=1, gx=6, gy=16)),
+        ((300, 1152, 384, 2), dict(family=TILE, u=1, ntw=2, nchunks=3, gx=9, gy=3, gz=2)),
+        ((40, 200, 192, 1), dict(family=TILE, u=1, ntw=1, nchunks=3, gx=4, gy=1)),
+        ((8300, 2112, 512, 1), dict(family=PF, gx=33 * 9)),           # (N % 64 == 0 is all the 256-row kernel asks)
+        ((8300, 2100, 512, 1), dict(family=TILE, u=4, ntw=2, gx=17, gy=65)),
+    ]
+    for args, want in rows:
+        rc, p = gemm(*args)
+        assert rc == 0, (args, lib.zk_last_error())
+        assert {k: p[k] for k in want} == want, (args, p)
+        if p["family"] != WS:
+            assert (p["mt"], p["ncw"]) == (0, 0) and (p["family"] == TILE or p["nchunks"] == 0), (args, p)
+
+    vrows = [
+        # B = 1 decode (2 rows): in_proj with the LayerNorm prologue (one tile, 12 k-steps in flight), out_proj
+        # (half tiles, 8 waves), fc1 (two tiles), fc2 (K = 8192, half tiles), the heads
+        ((2, 3072, 2048, 0, 1), dict(lay=1, ksw=64, xr=2, grid=192, block=256, ntw=1, half=0, nw=4, ks=16, pf=12)),
+        ((2, 2048, 2048, 2, 0), dict(lay=0, ksw=64, xr=2, grid=256, block=512, ntw=1, half=1, nw=8, ks=8, pf=4)),
+        ((2, 16384, 2048, 1, 1), dict(lay=2, ksw=64, xr=2, grid=512, block=256, ntw=2, half=0, nw=4, ks=16, pf=8)),
+        ((2, 2048, 8192, 2, 0), dict(lay=0, ksw=256, xr=2, grid=256, block=512, nw=8, ks=32, pf=8)),
+        ((16, 9234, 2048, 0, 1), dict(lay=2, ksw=64, xr=16, grid=289, block=256, ntw=2, pf=8)),
+        # the layout edges: 255 / 256 tiles, 511 / 512 tiles; SwiGLU never runs on half tiles
+        ((3, 4080, 4096, 0, 0), dict(lay=0, ksw=128, xr=16, grid=510)), ((3, 4096, 4096, 0, 0), dict(lay=1, grid=256)),
+        ((3, 8176, 2048, 2, 0), dict(lay=1, grid=511)), ((3, 8192, 2048, 2, 0), dict(lay=2, grid=256)),
+        ((3, 8208, 2048, 0, 0), dict(lay=2, grid=257)), ((2, 208, 2048, 1, 0), dict(lay=1, grid=13)),
+    ]
+    for args, want in vrows:
+        rc, p = gemv(*args)
+        assert rc == 0, (args, lib.zk_last_error())
+        assert {k: p[k] for k in want} == want, (args, p)
+        assert p["block"] == 64 * p["nw"] and p["ks"] * p["nw"] == p["ksw"] and p["ntw"] == (2 if p["lay"] == 2 else 1)
+
+    # what the entries refuse, the queries refuse: -1 and a message
+    for args in ((0, 10, 64, 1, 0), (4, 10, 100, 1, 0), (4, 10, 256, 3, 0), (4, 24, 256, 1, 1), (4, 32, 256, 2, 1),
+                 (4, 32, 256, 1, 2)):
+        rc, _ = gemm(*args)
+        assert rc == -1 and lib.zk_last_error().startswith(b"zk_gemm_plan:"), (args, rc, lib.zk_last_error())
+    for args in ((17, 64, 2048, 0, 0), (0, 64, 2048, 0, 0), (2, 64, 1024, 0, 0), (2, 40, 2048, 1, 0), (2, 64, 2048, 3, 0),
+                 (2, 64, 4096, 0, 1)):
+        rc, _ = gemv(*args)
+        assert rc == -1 and lib.zk_last_error().startswith(b"zk_gemv_plan:"), (args, rc, lib.zk_last_error())
+
+
 def test_gemm_warm_word_round_trip(lib):
     """The packed warm-up word (warm.h: chunks, NG, compute waves, grid tiles past N) is packed by
     zk_gemm_warm_desc and unpacked by warm_unit's accessors, which zk_gemm_warm_tiles runs on the host: the

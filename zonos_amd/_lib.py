@@ -184,6 +184,8 @@ _SIGS = {
     "zk_dac_rvq_decode_cl": [P, I, I, I, L, P, I, I, I, P, P, P],
     "zk_dac_conv_cl": [P, I, I, I, P, L, P, I, I, I, I, I, I, I, I, I, P, P, P, P, I, P, I, I, P],
     "zk_dac_conv_plan": [I, I, I, I, I, I, I, I, I, I, P],
+    "zk_gemm_plan": [I, I, I, I, I, P],
+    "zk_gemv_plan": [I, I, I, I, I, P],
     "zk_dac_tail_cl": [P, I, I, I, P, P, P, P, I, P],
     "zk_dac_resunit_cl": [P, I, I, I, P, P, I, P, P, P, P, P, P, I, P, I, P],
     "zk_dac_enc_conv1": [P, I, I, P, P, P, I, I, P, P, P],
@@ -268,6 +270,29 @@ def dac_conv_plan(B, Cin, Cout, ks, dil, Qn, nphase=1, resid=False, s_f32=False,
     plan = (C.c_int32 * len(DAC_PLAN_FIELDS))()
     call("zk_dac_conv_plan", int(fused), B, Cin, Cout, ks, dil, Qn, nphase, int(resid), int(s_f32), plan)
     return dict(zip(DAC_PLAN_FIELDS, plan))
+
+
+GEMM_FAMILIES = ("rk", "ws", "pf", "tile")       # k_gemv_rk, k_gemm_ws, k_gemm_pf, k_gemm
+GEMM_PLAN_FIELDS = ("family", "ks", "pf", "nchunks", "mt", "ncw", "u", "ntw", "gx", "gy", "gz", "block", "lds",
+                    "pf_cols")                   # ZK_GEMM_PLAN_N = 14
+GEMV_PLAN_FIELDS = ("lay", "ksw", "xr", "grid", "block", "ntw", "half", "nw", "ks", "pf")   # ZK_GEMV_PLAN_N = 10
+
+
+def gemm_plan(M, N, K, nsplit=1, mode=0) -> dict:
+    """zk_gemm_plan: the kernel family (a name of GEMM_FAMILIES), its template selectors and the grid
+    zk_gemm_bf16 launches a shape with. No GPU."""
+    plan = (C.c_int32 * len(GEMM_PLAN_FIELDS))()
+    call("zk_gemm_plan", M, N, K, nsplit, mode, plan)
+    d = dict(zip(GEMM_PLAN_FIELDS, plan))
+    d["family"] = GEMM_FAMILIES[d["family"]]
+    return d
+
+
+def gemv_plan(M, N, K, mode=0, ln=False) -> dict:
+    """zk_gemv_plan: the layout, template selectors and grid zk_gemv_fused launches a shape with. No GPU."""
+    plan = (C.c_int32 * len(GEMV_PLAN_FIELDS))()
+    call("zk_gemv_plan", M, N, K, mode, int(ln), plan)
+    return dict(zip(GEMV_PLAN_FIELDS, plan))
 
 
 def ptr(t) -> int | None:

@@ -1182,6 +1182,7 @@ extern "C" int zk_permute_fc1(const void* w_fc1, int F, int D, void* w_out, void
 bool zk_gemm_pf_applies(int M, int N, int K, int nsplit, int mode, long* tiles, int* block, int* lds);
 int zk_gemm_pf(const void* A, long lda, const void* W, int M, int N, int K, int mode, float* C, void* Cb,
                const int32_t* skip, void* stream);
+int zk_gemm_pf_tile_cols(int mode);
 
 namespace {
 
@@ -1350,14 +1351,36 @@ GemvPlan gemv_plan(int M, int N, int K, int mode, bool ln) {
 
 }  // namespace
 
+// The argument checks of zk_gemm_bf16 (`who`: the called entry, for its messages), shared with zk_gemm_plan.
+static int gemm_check(const char* who, long lda, int M, int N, int K, int nsplit, int mode) {
+    ZK_REQUIRE(M > 0 && N > 0 && K > 0, "%s: empty shape M=%d N=%d K=%d", who, M, N, K);
+    ZK_REQUIRE(nsplit >= 1 && K % (nsplit * BK) == 0, "%s: K=%d must be a multiple of nsplit*%d", who, K, BK);
+    ZK_REQUIRE(lda >= K && lda % 8 == 0, "%s: lda=%ld", who, lda);
+    ZK_REQUIRE(mode == 0 || (mode == 1 && nsplit == 1 && N % 16 == 0), "%s: bad mode/nsplit", who);
+    return 0;
+}
+
 int zk_gemm_bf16_warm(const void* A, long lda, const void* W, int M, int N, int K, int nsplit, int mode,
                       float* Cpart, void* Cout, const int32_t* skip_flag, ZkWarm warm, void* stream) {
-    ZK_REQUIRE(M > 0 && N > 0 && K > 0, "zk_gemm_bf16: empty shape M=%d N=%d K=%d", M, N, K);
-    ZK_REQUIRE(nsplit >= 1 && K % (nsplit * BK) == 0, "zk_gemm_bf16: K=%d must be a multiple of nsplit*%d", K, BK);
-    ZK_REQUIRE(lda >= K && lda % 8 == 0, "zk_gemm_bf16: lda=%ld", lda);
-    ZK_REQUIRE(mode == 0 || (mode == 1 && nsplit == 1 && N % 16 == 0), "zk_gemm_bf16: bad mode/nsplit");
+    ZK_TRY(gemm_check("zk_gemm_bf16", lda, M, N, K, nsplit, mode));
     return gemm_launch(gemm_plan(M, N, K, nsplit, mode), A, lda, W, M, N, K, nsplit, Cpart, Cout, skip_flag, warm,
                        (hipStream_t)stream);
+}
+
+// The plan zk_gemm_bf16 launches (M, N, K, nsplit, mode) by: the entry's own shape checks, the very GemmPlan of
+// the launch; touches no GPU. Fields a family does not have are 0.
+extern "C" int zk_gemm_plan(int M, int N, int K, int nsplit, int mode, int32_t* plan) {
+    ZK_REQUIRE(plan != nullptr, "zk_gemm_plan: null plan");
+    if (gemm_check("zk_gemm_plan", K, M, N, K, nsplit, mode) != 0) return -1;      // (a dense A: lda = K)
+    const GemmPlan p = gemm_plan(M, N, K, nsplit, mode);
+    const bool ws = p.family == GEMM_WS;
+    // (the decode-regime fields of a slice that falls through to k_gemm describe no launch: reported as 0)
+    const int32_t v[ZK_GEMM_PLAN_N] = {
+        (int32_t)p.family, p.ks, p.family == GEMM_PF ? 0 : (ws ? (mode ? WS_PF : WS_PF0) : p.pf),
+        ws ? p.nchunks : (p.family == GEMM_TILE ? K / nsplit / BK : 0), ws ? p.mt : 0, ws ? p.ncw : 0, p.u, p.ntw,
+        (int32_t)p.gx, p.gy, p.gz, p.block, (int32_t)p.lds, p.family == GEMM_PF ? zk_gemm_pf_tile_cols(mode) : 0};
+    std::copy(v, v + ZK_GEMM_PLAN_N, plan);
+    return 0;
 }
 
 extern "C" int zk_gemm_bf16(const void* A, long lda, const void* W, int M, int N, int K, int nsplit, int mode,
@@ -1412,18 +1435,27 @@ void gf_launch(int grid, int block, void* stream, const void* A, long lda, const
                            (const bf16_t*)ln_b, eps, Cf, (bf16_t*)Cb, skip, mw, mhkv, qk);
 }
 
+// The argument checks of zk_gemv_fused / zk_gemv_fused_w8 that a plan depends on (`who`: the called entry;
+// lda_max > 0: the largest row stride the stream's kernel takes; ln: 1 with the LayerNorm prologue, 0 without,
+// -1 only one of its two pointers given), in the entry's order, shared with zk_gemv_plan.
+int gemv_check(const char* who, long lda, long lda_max, int M, int N, int K, int mode, int ln) {
+    ZK_REQUIRE(M >= 1 && M <= 16 && N > 0, "%s: M=%d (1..16) N=%d", who, M, N);
+    ZK_REQUIRE(K == 2048 || K == 4096 || K == 8192, "%s: K=%d (2048, 4096 or 8192)", who, K);
+    ZK_REQUIRE(lda >= K && lda % 8 == 0 && (lda_max <= 0 || lda <= lda_max), "%s: lda=%ld", who, lda);
+    ZK_REQUIRE(mode >= 0 && mode <= 2, "%s: mode %d", who, mode);
+    ZK_REQUIRE(mode != 1 || N % 16 == 0, "%s: SwiGLU needs N %% 16 == 0", who);
+    ZK_REQUIRE(ln >= 0, "%s: LN needs both w and b", who);
+    ZK_REQUIRE(!ln || K == 2048, "%s: LN prologue needs K = 2048 (K=%d)", who, K);
+    return 0;
+}
+
 template <class WS>
 int gemv_fused(const char* who, const void* A, long lda, const void* W, const void* wsc, int M, int N, int K, int mode,
                const void* ln_w, const void* ln_b, float eps, float* Cf, void* Cb, const int32_t* skip_flag,
                void* stream) {
-    ZK_REQUIRE(M >= 1 && M <= 16 && N > 0, "%s: M=%d (1..16) N=%d", who, M, N);
-    ZK_REQUIRE(K == 2048 || K == 4096 || K == 8192, "%s: K=%d (2048, 4096 or 8192)", who, K);
     // (a scaled stream's kernel takes lda as an int)
-    ZK_REQUIRE(lda >= K && lda % 8 == 0 && (!WS::SCALED || lda <= (1L << 30)), "%s: lda=%ld", who, lda);
-    ZK_REQUIRE(mode >= 0 && mode <= 2, "%s: mode %d", who, mode);
-    ZK_REQUIRE(mode != 1 || N % 16 == 0, "%s: SwiGLU needs N %% 16 == 0", who);
-    ZK_REQUIRE((ln_w == nullptr) == (ln_b == nullptr), "%s: LN needs both w and b", who);
-    ZK_REQUIRE(ln_w == nullptr || K == 2048, "%s: LN prologue needs K = 2048 (K=%d)", who, K);
+    ZK_TRY(gemv_check(who, lda, WS::SCALED ? (1L << 30) : 0, M, N, K, mode,
+                      (ln_w == nullptr) != (ln_b == nullptr) ? -1 : (ln_w != nullptr ? 1 : 0)));
     ZK_REQUIRE(mode == 0 ? Cf != nullptr : Cb != nullptr, "%s: missing output", who);
     ZK_REQUIRE(!WS::SCALED || (W != nullptr && wsc != nullptr), "%s: missing weight image or scales", who);
     const GemvPlan p = gemv_plan(M, N, K, mode, ln_w != nullptr);
@@ -1496,6 +1528,21 @@ extern "C" int zk_gemv_fused(const void* A, long lda, const void* W, int M, int 
                              const int32_t* skip_flag, void* stream) {
     return gemv_fused<WsBf16>("zk_gemv_fused", A, lda, W, nullptr, M, N, K, mode, ln_w, ln_b, eps, Cf, Cb, skip_flag,
                               stream);
+}
+// The plan zk_gemv_fused launches (M, N, K, mode, LayerNorm prologue or not) by: the entry's own shape checks,
+// the very GemvPlan and GfForm of the launch; touches no GPU.
+extern "C" int zk_gemv_plan(int M, int N, int K, int mode, int ln, int32_t* plan) {
+    ZK_REQUIRE(plan != nullptr, "zk_gemv_plan: null plan");
+    if (gemv_check("zk_gemv_plan", K, 0, M, N, K, mode, ln != 0 ? 1 : 0) != 0) return -1;          // (a dense A: lda = K)
+    const GemvPlan p = gemv_plan(M, N, K, mode, ln != 0);
+    if (!gf_has(mode, ln != 0, p.lay, p.ksw)) {
+        zk_set_error("zk_gemv_plan: no kernel for K=%d", K);
+        return -1;
+    }
+    const GfForm f = gf_form(p.lay, ln != 0, p.ksw, p.xr);
+    const int32_t v[ZK_GEMV_PLAN_N] = {p.lay, p.ksw, p.xr, p.grid, p.block, f.ntw, f.half ? 1 : 0, f.nw, f.ks, f.pf};
+    std::copy(v, v + ZK_GEMV_PLAN_N, plan);
+    return 0;
 }
 extern "C" int zk_gemv_fused_w8(const void* A, long lda, const void* W8, const void* w_scale, int M, int N, int K,
                                 int mode, const void* ln_w, const void* ln_b, float eps, float* Cf, void* Cb,

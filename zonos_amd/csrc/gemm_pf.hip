@@ -392,6 +392,10 @@ bool zk_gemm_pf_applies(int M, int N, int K, int nsplit, int mode, long* tiles, 
     return *tiles >= 256;                             // at least one tile per CU
 }
 
+// Columns of the tile zk_gemm_pf runs mode `mode` with (zk_gemm_plan reports it)
+constexpr int PF_NTN0 = 4, PF_NTN1 = 4;
+int zk_gemm_pf_tile_cols(int mode) { return mode == 0 ? pf_bn<PF_NTN0> : pf_bn<PF_NTN1>; }
+
 template <int MODE, int NTN>
 static int pf_launch(const void* A, long lda, const void* W, int M, int N, int K, float* C, void* Cb,
                       const int32_t* skip, hipStream_t stream) {
@@ -414,8 +418,8 @@ int zk_gemm_pf(const void* A, long lda, const void* W, int M, int N, int K, int 
     // overlapping the other's MFMAs -- measured 1-3 % slower: DESIGN.md §6 round 4)
     const hipStream_t st = (hipStream_t)stream;
     int rc;
-    if (mode == 0) rc = pf_launch<0, 4>(A, lda, W, M, N, K, C, Cb, skip, st);
-    else rc = pf_launch<1, 4>(A, lda, W, M, N, K, C, Cb, skip, st);
+    if (mode == 0) rc = pf_launch<0, PF_NTN0>(A, lda, W, M, N, K, C, Cb, skip, st);
+    else rc = pf_launch<1, PF_NTN1>(A, lda, W, M, N, K, C, Cb, skip, st);
     if (rc) return rc;
     ZK_CHECK_LAUNCH("zk_gemm_bf16 (prefill)");
     return 0;
